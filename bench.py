@@ -8,11 +8,17 @@ all-reduce] -> clip_grad_norm(1.0) -> AdamW, exactly the per-batch body of the r
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task description) carrying two extra objects:
+Rank 0 prints ONE JSON line: metric, value (images/s), unit, higher_is_better, dtype, ms_per_step (one timed step) and the
+run's configuration.  A plain run sets up, warms up, times --steps steps and reports them.  With --full it then measures
+the step's surroundings and adds to the line:
   roofline      dominant kernel: algorithmic FLOPs per launch / average launch duration measured
                 with HIP events on the launch stream in an instrumented replay of the same plan
+                (--kernel-table prints the whole table to stderr)
   cpu_baseline  the CPU oracle (plain torch fp32 restatement of the reference) timed on this
                 box's host cores on a bounded sample of the same workload
+  config.host_issue_ms_per_step   host time to issue one step on an idle queue
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs), from inputs that
+are the same in every run with the same arguments, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -226,6 +232,35 @@ def cpu_baseline(model, hw, steps=3):
             "step_seconds": [round(t, 3) for t in times]}
 
 
+DUMP_SAMPLE = 1 << 22          # elements per dumped array at most (16 MB of float32; four arrays stay under 64 MB)
+
+
+def dump_outputs(outdir, loss, out, params):
+    """What a caller of the train step holds after the last timed step, as float32 .npy files: the loss, the logits (whole
+    up to DUMP_SAMPLE elements, else a fixed seeded sample), and the same fixed seeded sample of the updated parameters and
+    of their gradients (all parameters flattened in model.parameters() order; frozen ones carry zero gradients)."""
+    import numpy as np
+
+    def sample(t):
+        t = t.reshape(-1)
+        if t.numel() <= DUMP_SAMPLE:
+            return t
+        idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+        return t[idx.to(t.device)]
+
+    params = list(params)
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "logits": out.detach().float() if out.numel() <= DUMP_SAMPLE else sample(out.detach().float()),
+        "params_sample": sample(torch.cat([p.detach().float().reshape(-1) for p in params])),
+        "grads_sample": sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                                          for p in params])),
+    }
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -235,8 +270,12 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--model", default="AttentionUNet")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel roofline, the host issue time and the CPU-oracle "
+                         "baseline (off: the run does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the per-kernel roofline")
     ap.add_argument("--serial-streams", action="store_true",
                     help="keep the weight-gradient launches on the main stream (MI355_SIDE_STREAM=0): per-kernel durations "
                          "in a rocprofv3 trace are then not inflated by the wgrad / dgrad overlap of the production schedule")
@@ -246,6 +285,10 @@ def main():
     ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel time table to stderr")
     ap.add_argument("--force-dp", action="store_true", help="exercise the RCCL data-parallel path even with one rank")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.kernel_table or args.split_by_shape) and not args.full:
+        ap.error("--kernel-table / --split-by-shape print the per-kernel profile, which runs with --full only")
     if args.serial_streams:
         os.environ["MI355_SIDE_STREAM"] = "0"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -302,7 +345,7 @@ def main():
         moptim.clip_grad_norm_(model.parameters(), max_norm=1.0, inv_scale=inv_scale)
         scaler.step(opt)
         scaler.update()
-        return loss
+        return loss, out
 
     def log(msg):
         if rank == 0:
@@ -319,18 +362,18 @@ def main():
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            static_loss = step()
-        runner = lambda: (g.replay(), static_loss)[1]
+            static_outputs = step()
+        runner = lambda: (g.replay(), static_outputs)[1]
 
     for _ in range(args.warmup):
-        loss = runner()
+        runner()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = runner()
+        loss, out = runner()
     issue_ms = (time.perf_counter() - t0) / args.steps * 1e3      # host time to ISSUE a step (== ms_per_step when launch-bound)
     torch.cuda.synchronize()
     if world > 1:
@@ -342,18 +385,24 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     final_loss = float(loss.detach())
-    # host cost of ISSUING one step, measured on an empty queue (over many back-to-back steps the runtime's bounded launch queue
-    # makes the host wait for the GPU, so `issue_ms` above converges to the GPU time and says nothing about the host)
-    one = []
-    for _ in range(3):
+    log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step ({issue_ms:.2f} ms/step to issue over the back-to-back "
+        f"region, bounded by the launch queue)")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, out, model.parameters())
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    issue_one_ms = None
+    if args.full:
+        # host cost of ISSUING one step, measured on an empty queue (over many back-to-back steps the runtime's bounded launch
+        # queue makes the host wait for the GPU, so `issue_ms` above converges to the GPU time and says nothing about the host)
+        one = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            runner()
+            one.append((time.perf_counter() - t1) * 1e3)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        runner()
-        one.append((time.perf_counter() - t1) * 1e3)
-    torch.cuda.synchronize()
-    issue_one_ms = min(one)
-    log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step (host time to issue ONE step on an idle queue "
-        f"{issue_one_ms:.2f} ms; {issue_ms:.2f} ms/step over the back-to-back region, bounded by the launch queue)")
+        issue_one_ms = min(one)
+        log(f"host time to issue ONE step on an idle queue: {issue_one_ms:.2f} ms")
 
     result = None
     if rank == 0:
@@ -370,9 +419,11 @@ def main():
                                    f"bs={args.batch}/GPU, NHWC {args.dtype} activations, fp32 master weights",
                        "global_batch": args.batch * world, "parallelism": f"dp{world}", "hip_graph": bool(args.graph),
                        "wgrad_side_stream": os.environ.get("MI355_SIDE_STREAM", "1") != "0",
-                       "final_loss": round(final_loss, 5), "host_issue_ms_per_step": round(issue_one_ms, 3),
+                       "final_loss": round(final_loss, 5),
                        "plan_replay": "C (mi355_plan_run)" if os.environ.get("MI355_PLAN_C", "1") != "0" else "python loop"},
         }
+        if issue_one_ms is not None:
+            result["config"]["host_issue_ms_per_step"] = round(issue_one_ms, 3)
         if dp is not None:                        # fp32 = parity mode (default); MI355_DP_BUCKET_DTYPE=bf16: two-byte buckets on the wire
             result["config"]["grad_bucket_dtype"] = {None: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}[dp.wire_dtype]
         if args.model == "AttentionUNet":         # (SURVEY.md 8d gives the per-image FLOPs of this model only)
@@ -380,7 +431,7 @@ def main():
             result["config"]["step_mfma_frac"] = round(step_tflops / PEAK_TFLOPS[args.dtype], 4)
 
     # ---- per-kernel roofline (instrumented replay of the same plan, rank 0) -----------------------------
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         plan = [p for p in model.engine.plans.values() if p.training and p.dout is not None][0]
         global SPLIT_BY_SHAPE
         SPLIT_BY_SHAPE = args.split_by_shape
@@ -438,7 +489,7 @@ def main():
         result["roofline"]["plan_kernel_ms_per_step"] = round(sum(v[0] for v in agg.values()) / 2, 3)
         result["roofline"]["plan_chip_ms_per_step"] = round(total / 2, 3)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("per-kernel profile done; timing the CPU oracle baseline")
         if args.model in CPU_CONFIGS:
             result["cpu_baseline"] = cpu_baseline(args.model, args.size)

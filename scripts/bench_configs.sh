@@ -8,7 +8,7 @@ out=gpurun_out/${tag}_other_configs.txt
 run() {
   name=$1; shift
   echo "## $name: bench.py $*" >> $out
-  python bench.py --steps 10 --warmup 3 --kernel-table --table-rows 30 "$@" > gpurun_out/${tag}_${name}.json 2> gpurun_out/${tag}_${name}_kernel_table.txt || { echo "FAILED" >> $out; return; }
+  python bench.py --full --steps 10 --warmup 3 --kernel-table --table-rows 30 "$@" > $(dirname $out)/${tag}_${name}.json 2> $(dirname $out)/${tag}_${name}_kernel_table.txt || { echo "FAILED" >> $out; return; }
   python - gpurun_out/${tag}_${name}.json >> $out <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

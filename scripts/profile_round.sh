@@ -19,12 +19,12 @@ python3 scripts/pmc_traffic.py "$out/pmc_fetch/**/*counter_collection.csv" "$out
 python3 scripts/pmc_agg.py "$out/pmc_fetch/**/*counter_collection.csv" > $out/${tag}_pmc_fetch_size.txt
 python3 scripts/pmc_agg.py "$out/pmc_write/**/*counter_collection.csv" > $out/${tag}_pmc_write_size.txt
 cp profiles/${tag}_pmc_traffic.json $out/
-$B --steps 20 --warmup 5 --kernel-table > $out/${tag}_bench_n1_bf16.json 2> $out/${tag}_bench_n1_bf16_kernel_table.txt
+$B --full --steps 20 --warmup 5 --kernel-table > $out/${tag}_bench_n1_bf16.json 2> $out/${tag}_bench_n1_bf16_kernel_table.txt
 echo "[profile] bench done: $(cut -c1-120 $out/${tag}_bench_n1_bf16.json)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/serial -- $B --steps 10 --warmup 3 --no-cpu-baseline --serial-streams > $out/${tag}_bench_n1_bf16_serial_profiled.json 2> $out/serial.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/serial -- $B --full --steps 10 --warmup 3 --no-cpu-baseline --serial-streams > $out/${tag}_bench_n1_bf16_serial_profiled.json 2> $out/serial.log
 cp $(find $out/serial -name "*kernel_stats.csv" | head -1) $out/${tag}_bench_n1_bf16_serial_kernel_stats.csv
 echo "[profile] serial rocprof done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prod -- $B --steps 10 --warmup 3 --no-cpu-baseline > $out/${tag}_bench_n1_bf16_profiled.json 2> $out/prod.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prod -- $B --full --steps 10 --warmup 3 --no-cpu-baseline > $out/${tag}_bench_n1_bf16_profiled.json 2> $out/prod.log
 cp $(find $out/prod -name "*kernel_stats.csv" | head -1) $out/${tag}_bench_n1_bf16_kernel_stats.csv
 rm -rf $out/pmc_fetch $out/pmc_write $out/serial $out/prod
 ls -la $out
