@@ -110,7 +110,8 @@ int mi355_conv2d_igemm_variant_n(int N, int Hi, int Wi, int Ci, int Ho, int Wo, 
 /* Fused BatchNorm statistics: when `stats` != NULL the epilogue also writes, per M tile b of the kernel
  * (per WORKGROUP for the streaming pointwise kernel) it dispatches to, stats[(b*2+0)*Co + c] = sum and stats[(b*2+1)*Co + c] = sum of squares of the
  * (rounded) outputs — the same partial layout mi355_bn_finalize consumes.  The number of tile rows is
- * mi355_conv2d_igemm_stat_rows(...) (0 = not available for this shape/dtype: use mi355_bn_stats). */
+ * mi355_conv2d_igemm_stat_rows(...) (0 = not available for this shape/dtype: use mi355_bn_stats; the launcher refuses a `stats`
+ * buffer exactly there, and with the accumulate bit). */
 /* Output-channel tile (128 / 64 / 32) of the LDS-DMA ring kernel (variant 1) for N x Ho x Wo output rows: the widest that divides
  * Co unless its grid would leave most of the chip idle (bench.py's kernel names). */
 int mi355_conv2d_igemm_dma_tile(int N, int Ho, int Wo, int Ci, int Co);

@@ -667,9 +667,11 @@ extern "C" int mi355_conv2d_igemm_variant_n(int N, int Hi, int Wi, int Ci, int H
 extern "C" int mi355_conv2d_igemm_dma_tile(int N, int Ho, int Wo, int Ci, int Co) { return dma_tile_n((long long)N * Ho * Wo, Ci, Co); }
 extern "C" int mi355_conv2d_igemm_generic_tile(int N, int Ho, int Wo, int Co) { return small_grid_tile_n((long long)N * Ho * Wo, Co); }
 
-extern "C" int mi355_conv2d_igemm_stat_rows(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul,
-                                            int kmul, int off, int div, int up, int dtype) {
-  switch (final_variant(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype)) {
+// Statistics partial rows the variant v leaves for this shape (0 = no statistics epilogue).  The launcher refuses a `stats`
+// buffer exactly where this is 0, so query and launcher cannot disagree.
+static int stat_rows_of(IgemmVariant v, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul,
+                        int off, int div, int up) {
+  switch (v) {
     case IG_HALO_PP:
     case IG_HALO_PP128: return N * (Ho / 16) * (Wo / 32);
     case IG_WS128: return ws_groups(N, Ho, Wo, Co, 4, device_cus());      // persistent kernels: one row per workgroup range
@@ -682,6 +684,12 @@ extern "C" int mi355_conv2d_igemm_stat_rows(int N, int Hi, int Wi, int Ci, int H
       return gemm256_mode(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up) == 1 ? (int)((long long)N * Ho * Wo / 256) : 0;
     default: return 0;       // generic kernel: no fused statistics, run mi355_bn_stats
   }
+}
+
+extern "C" int mi355_conv2d_igemm_stat_rows(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul,
+                                            int kmul, int off, int div, int up, int dtype) {
+  return stat_rows_of(final_variant(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype), N, Hi, Wi, Ci, Ho, Wo, Co,
+                      KH, KW, mul, kmul, off, div, up);
 }
 
 extern "C" int mi355_conv2d_igemm(const void* in, const void* wk, const float* bias, void* out, int N, int Hi, int Wi,
@@ -708,7 +716,7 @@ extern "C" int mi355_conv2d_igemm(const void* in, const void* wk, const float* b
   MI355_CHECK_ARG(!halo_family(v) || image_fits_descriptor(Hi, Wi, ldi, esz),
                   "conv2d_igemm: an image of %d x %d pixels at a channel stride of %d is 2 GiB or more: beyond the 32-bit lane offsets of "
                   "the halo kernels' buffer descriptors", Hi, Wi, ldi);
-  MI355_CHECK_ARG(!stats || (v != IG_GENERIC && !(accumulate & 1)),
+  MI355_CHECK_ARG(!stats || (stat_rows_of(v, N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up) > 0 && !(accumulate & 1)),
                   "conv2d_igemm: fused statistics are not available for this shape/dtype (mi355_conv2d_igemm_stat_rows == 0)");
   ConvArgs a;
   a.in = in; a.wk = wk; a.bias = bias; a.out = out;
