@@ -402,6 +402,24 @@ int mi355_gather_rows(const float* x, const int32_t* idx, int n, long long row, 
 int mi355_mask_scatter(const float* logit, const int32_t* idx, int n, long long per, float thr, uint8_t* out,
                        mi355_stream_t s);
 
+/* ---- Grad-CAM and image overlays (utils/explain.py; utils/pipeline.py process_images, reference pipeline.py:399-407) ---------- */
+/* dout[b][k] = (k == t_b) for the explained class t_b = target[b] when target is given (out of [0, K): a zero row, t_b = -1),
+ * else the first maximum of logits[b][.]; target_out[b] = t_b (int32). */
+int mi355_cam_seed(const float* logits, const int32_t* target, int B, int K, float* dout, int32_t* target_out, mi355_stream_t s);
+/* Per image n of NHWC maps A, dA (compute dtype, channel strides ldA, lddA >= C): alpha[c] = mean_p dA[p][c],
+ * raw[p] = relu(sum_c alpha[c] A[p][c]), cam_lowres[n][p] = (raw[p] - min raw) / (1e-7 + max raw - min raw), fp32 throughout.
+ * MI355_ERR_UNSUPPORTED when 4 * (HW + C) exceeds the kernel's 48 KB of LDS. */
+int mi355_gradcam(const void* A, int ldA, const void* dA, int lddA, int N, int HW, int C, int dtype, float* cam_lowres,
+                  mi355_stream_t s);
+/* dst[N][H][W] = F.interpolate(src[N][h][w], (H, W), mode="bilinear", align_corners=False) (fp32; any sizes). */
+int mi355_resize_bilinear_f32(const float* src, int N, int h, int w, float* dst, int H, int W, mi355_stream_t s);
+/* uint8 RGB [B][H][W][3]: where mask[b][(y h) / H][(x w) / W] == 255, R = sat(rint(R + 255 * opacity)); every other byte copied. */
+int mi355_overlay_mask(const uint8_t* img, int B, int H, int W, const uint8_t* mask, int h, int w, float opacity, uint8_t* out,
+                       mi355_stream_t s);
+/* uint8 RGB [B][H][W][3], cam fp32 [B][H][W] in [0, 1]: out = sat(rint((1 - alpha) img + alpha 255 jet(cam))) per channel, jet =
+ * matplotlib's 256-entry LUT indexed by min(int(256 cam), 255). */
+int mi355_overlay_heatmap(const uint8_t* img, int B, int H, int W, const float* cam, float alpha, uint8_t* out, mi355_stream_t s);
+
 /* ---- segmentation metrics counters (utils/tester.py:92-193; helpers.py:223-227) ------------- */
 /* per sample b: counts[b*4+{0,1,2,3}] = tp, pred-positive, target-positive, equal   (p = prob > thr) */
 int mi355_seg_counts(const float* prob_or_logit, const float* target, float* counts, int B, long long per,

@@ -107,16 +107,24 @@ class Engine:
         return self._drop_seed, self._drop_counter
 
     # ---- plans --------------------------------------------------------------------------------------------
-    def plan_for(self, x_shape, training, want_grad, dtype):
-        sig = tuple(p.requires_grad for p in self.params) if want_grad else ()
-        key = (tuple(x_shape), training, want_grad, dtype, sig)
+    def plan_for(self, x_shape, training, want_grad, dtype, explain=False):
+        """``explain``: the Grad-CAM plan (eval semantics, no parameter gradients, the head's backward down to the CAM tap)."""
+        if explain:
+            training = want_grad = False
+            key = (tuple(x_shape), "explain", dtype)
+        else:
+            sig = tuple(p.requires_grad for p in self.params) if want_grad else ()
+            key = (tuple(x_shape), training, want_grad, dtype, sig)
         plan = self.plans.get(key)
         if plan is None or plan.params_moved():
-            b = graph.Builder(self, self.flat_p.device, dtype, training, want_grad)
+            b = graph.Builder(self, self.flat_p.device, dtype, training, want_grad, explain=explain)
             xin = b.set_input(x_shape)
             self.net.build(b, xin)
             if b.output is None:
                 raise RuntimeError(f"{type(self.net).__name__}.build() did not define an output")
+            if explain and b.cam is None:
+                raise NotImplementedError(f"Grad-CAM: {type(self.net).__name__} has no CAM tap (Builder.cam_tap); only the classifiers "
+                                          "can be explained")
             plan = b.finish()
             plan.has_dropout = self._drop_counter is not None and any(l.name == "mi355_dropout_fwd" for l in plan.fwd)
             self.plans[key] = plan
@@ -161,6 +169,29 @@ class Engine:
         out = _NetFn.apply(self, plan, x, *self.params)
         out._mi355_plan = plan
         return out
+
+    def explain(self, x, target=None):
+        """Grad-CAM at the head's input, eval semantics whatever ``net.training`` says, on the current stream (no host sync).
+        ``target``: None (each sample's first-maximum logit) or an int32 CUDA tensor [B] of classes (one outside [0, K) gives a
+        target of -1 and an all-zero map).  Returns (logits fp32 [B,K], target int32 [B], cam_lowres fp32 [B,h,w] in [0, 1])."""
+        if x.device.type != "cuda":
+            raise RuntimeError("the MI355X path needs CUDA/HIP tensors (there is no CPU fallback); "
+                               "move the model and its input to a GPU device")
+        self._check_storage()
+        net = self.net
+        plan = self.plan_for(x.shape, False, False, net.compute_dtype or _DEFAULT_DTYPE, explain=True)
+        if target is not None:
+            if not (isinstance(target, torch.Tensor) and target.dtype == torch.int32 and target.device == plan.device
+                    and target.is_contiguous() and target.numel() == x.shape[0]):
+                raise TypeError(f"explain: target must be a contiguous int32 tensor of {x.shape[0]} classes on {plan.device}")
+        logits = self.run_forward(plan, x)
+        plan.run_explain(self._stream(), target.data_ptr() if target is not None else None)
+        t = plan.cam
+        cam = plan.cam_lowres[: t.N * t.H * t.W].view(t.N, t.H, t.W)
+        tgt = plan.cam_target[: t.N]
+        if net.clone_eval_output:
+            return logits.clone(), tgt.clone(), cam.clone()
+        return logits, tgt, cam
 
 
 class _NetFn(torch.autograd.Function):
@@ -217,6 +248,10 @@ class Net(nn.Module):
 
     def forward(self, x):
         return self.engine.forward(x)
+
+    def explain(self, x, target=None):
+        """Grad-CAM of the classifiers (utils/explain.py GradCAM): see Engine.explain."""
+        return self.engine.explain(x, target)
 
     def plan_summary(self, x_shape, training=True):
         """(forward launches, backward launches) of the plan for an input shape (host-side only)."""

@@ -145,6 +145,11 @@ class Plan:
         self.output = b.output            # ("z", tensor[M], N,H,W) or ("v", V)
         self.dout = b.dout                # fp32 buffer the loss writes dL/dlogits into
         self.input_grad = getattr(b, "input_grad", None)   # NCHW fp32 dL/dx when requested
+        self.explain = b.explain
+        self.cam = self.cam_grad = self.cam_target = self.cam_lowres = None
+        if b.cam is not None:             # explain plan: the tapped map, its gradient (compute dtype, NHWC, channel stride ld), the CAM
+            self.cam, self.cam_grad = b.cam, b.grad_of(b.cam)
+            self.cam_target, self.cam_lowres = b.cam_target, b.cam_lowres          # int32 [N], fp32 [N, H, W]
         self.ws = {k: (torch.empty(max(n, 16), dtype=torch.uint8 if k == "bytes" else torch.float32, device=b.device))
                    for k, n in b.ws_need.items()}
         self.param_ptrs = [(p, p.data_ptr()) for p in b.params_seen]
@@ -315,6 +320,23 @@ class Plan:
         else:
             self.run_calls_two_streams(calls[first:last])
 
+    def run_explain(self, stream, target_ptr=None):
+        """Backward of an explain plan (seed, head backward, Grad-CAM); ``target_ptr``: int32 [N] classes to explain, or None for
+        the argmax (the seed launch's target slot is patched, like the forward's input pointer)."""
+        calls = self.bind(stream)[1]
+        if self.replay_in_c:
+            _, cp, _ = self._cplans[int(stream or 0)]
+            lib.raw("mi355_plan_patch")(cp, 0, 1, int(target_ptr or 0))
+            rc = lib.raw("mi355_plan_run")(cp, 0, len(calls), stream, None)
+            if rc:
+                self._c_fail(cp, rc, calls)
+            return
+        fn, args, name, _ = calls[0]
+        rc = fn(args[0], target_ptr, *args[2:])
+        if rc:
+            raise RuntimeError(f"{name} failed (rc={rc}): {lib.raw('mi355_last_error')().decode()}")
+        self._run(calls[1:])
+
     def join_side(self):
         if self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)
@@ -342,7 +364,7 @@ class Builder:
     """Emits forward launches and registers reverse-mode rules; `finish()` returns a Plan."""
     fuse_residual = FUSE_RESIDUAL
 
-    def __init__(self, engine, device, dtype, training, want_grad):
+    def __init__(self, engine, device, dtype, training, want_grad, explain=False):
         self.engine = engine
         self.device = torch.device(device)
         self.dtype = dtype
@@ -351,6 +373,9 @@ class Builder:
         self.epc = 16 // self.esz
         self.training = training
         self.want_grad = want_grad and training
+        # explain plan (Grad-CAM): eval semantics, no parameter gradients; backward rules are recorded only behind cam_tap()
+        self.explain = bool(explain) and not training
+        self.cam = None                  # the tapped activation (explain plans)
         self.pre: List[Launch] = []
         self.fwd: List[Launch] = []
         self.bwd: List[Launch] = []
@@ -458,9 +483,29 @@ class Builder:
             if p is not None:
                 self.params_seen.append(p)
 
+    def param_grad(self, p):
+        """Does parameter p receive a gradient in this plan?  (never in an explain plan: Engine.flat_g stays untouched)"""
+        return p.requires_grad and not self.explain
+
+    @property
+    def recording(self):
+        """Are backward rules being recorded?  (training plans with gradients; explain plans from the CAM tap on)"""
+        return self.want_grad or self.cam is not None
+
     def rule(self, fn):
-        if self.want_grad:
+        if self.recording:
             self._rules.append(fn)
+
+    def cam_tap(self, t):
+        """The feature map a classifier's head consumes (Grad-CAM's target layer).  A no-op in training and eval plans; in an
+        explain plan the ONLY tensor that needs a gradient: the head's backward rules are recorded from here on, nothing upstream."""
+        if not self.explain:
+            return t
+        if self.cam is not None:
+            raise NotImplementedError("one CAM tap per model")
+        t.needs_grad = True
+        self.cam = t
+        return t
 
     # ---- input / output ----------------------------------------------------------------------------
     def set_input(self, x_shape):
@@ -583,12 +628,12 @@ class Builder:
         self.fwd.append(Launch("mi355_conv2d_igemm", x, wf, bias, y, x.N, x.H, x.W, x.C, x.ld, Ho, Wo, Co, y.ld,
                                k, k, s, 1, -p, 1, 1 if up else 0, 2 if relu else 0, stat_part, self.code, flops=flops, nbytes=nbytes,
                                tag=self.igemm_tag(x.N, x.H, x.W, x.C, Ho, Wo, Co, k, s, 1, -p, 1, 1 if up else 0)))
-        y.needs_grad = x.needs_grad or conv.weight.requires_grad
+        y.needs_grad = x.needs_grad or self.param_grad(conv.weight)
         self._conv_uses[id(conv)] = self._conv_uses.get(id(conv), 0) + 1
 
         def bwd(dy, bias_done=False):
             uses = self._conv_uses[id(conv)]
-            if (conv.weight.requires_grad and 1 < uses <= 6 and self.multi_wgrad and k == 3 and s == 1 and p == 1 and self.esz == 2
+            if (self.param_grad(conv.weight) and 1 < uses <= 6 and self.multi_wgrad and k == 3 and s == 1 and p == 1 and self.esz == 2
                     and lib.mi355_conv2d_wgrad_multi_ok(x.N, Ho, Wo, self.code)):
                 # a convolution applied several times (recurrent block): ONE weight-gradient launch over all (x, dy) pairs, emitted
                 # with the last application's backward (the first in forward order), ONE set of partial slabs, ONE reduce
@@ -598,7 +643,7 @@ class Builder:
                 if len(pend) == uses:
                     self._emit_multi_wgrad(conv, pend, Ho, Wo, Co, k, up, flops, nbytes)
                     del self._pending_wgrad[id(conv)]
-            elif conv.weight.requires_grad:
+            elif self.param_grad(conv.weight):
                 splits = lib.mi355_conv2d_wgrad_splits(x.N, Ho, Wo, x.C, Co, k, k)
                 ws = self.ws_bytes(splits * Co * k * k * x.C * 4)
                 self.bwd.append(Launch("mi355_conv2d_wgrad", x, dy, ws, splits, x.N, x.H, x.W, x.C, x.ld, Ho, Wo, Co, dy.ld,
@@ -606,7 +651,7 @@ class Builder:
                                        tag=self.wgrad_tag(Co, x.C, k, s, Ho, Wo, x.N, p), cus=self.wgrad_cus(x.N, Ho, Wo, x.C, Co, k, s, p, splits)))
                 ref, beta = self.pgrad(conv.weight)
                 self.bwd.append(Launch("mi355_conv2d_wgrad_reduce", ws, splits, ref, Co, x.C, conv.in_channels, k, k, 0, beta, side=True))
-            if conv.bias is not None and conv.bias.requires_grad and not bias_done:
+            if conv.bias is not None and self.param_grad(conv.bias) and not bias_done:
                 self.bias_grad_from(dy, conv.bias)
             if x.needs_grad:
                 if up:
@@ -737,20 +782,20 @@ class Builder:
             self.bwd.append(Launch("mi355_gate_bn_bwd_reduce", dz, y, y.ld, None, 0, *co, hconv.weight, part, y.M, C, self.code,
                                    nbytes=y.M * C * self.esz + 4 * y.M))
             head_folds = []
-            if hconv.weight.requires_grad:
+            if self.param_grad(hconv.weight):
                 wref, wbeta = self.pgrad(hconv.weight)
                 head_folds.append(Launch("mi355_colsum_finalize", self._ws_off(part, 3 * C * 4), nb, 5, C, wref, wbeta, side=SIDE_COLSUM))
                 if hconv.bias is not None:
                     bref2, bbeta = self.pgrad(hconv.bias)
                     head_folds.append(Launch("mi355_colsum_finalize", self._ws_off(part, 4 * C * 4), nb, 5 * C, 1, bref2, bbeta, side=SIDE_COLSUM))
             sums = self.f32(2 * C)
-            need_pg = bn.weight.requires_grad
+            need_pg = self.param_grad(bn.weight)
             if need_pg:
                 gref, gbeta = self.pgrad(bn.weight)
                 bref, _ = self.pgrad(bn.bias)
             self.bwd.append(Launch("mi355_bn_bwd_finalize_at", part, min(nb, lib.mi355_gate_bn_bwd_reduce_rows(y.M)), 5, 0, 1, C, sums,
                                    gref if need_pg else None, bref if need_pg else None, gbeta if need_pg else 0.0))
-            if bias is not None and bias.requires_grad and id(bias) not in self._grad_first:
+            if bias is not None and self.param_grad(bias) and id(bias) not in self._grad_first:
                 self.pgrad(bias)
                 self.zero_grad_params.append(bias)
             dy = self.grad_of(y)
@@ -765,14 +810,14 @@ class Builder:
                                    st["scale"], st["shift"], part, y.N, y.H, y.W, C, self.code,
                                    nbytes=int((1.25 + (da is not None)) * y.M * C * self.esz)))
             sums = self.f32(2 * C)
-            need_pg = bn.weight.requires_grad
+            need_pg = self.param_grad(bn.weight)
             if need_pg:
                 gref, gbeta = self.pgrad(bn.weight)
                 bref, _ = self.pgrad(bn.bias)
             self.bwd.append(Launch("mi355_bn_bwd_finalize", part, min(nb, lib.mi355_bn_bwd_reduce_pool2_rows(y.M)), C, sums,
                                    gref if need_pg else None, bref if need_pg else None, gbeta if need_pg else 0.0))
             dy = self.grad_of(y)
-            if bias is not None and bias.requires_grad and id(bias) not in self._grad_first:
+            if bias is not None and self.param_grad(bias) and id(bias) not in self._grad_first:
                 self.pgrad(bias)
                 self.zero_grad_params.append(bias)
             self.bwd.append(Launch("mi355_bn_bwd_apply_pool2", da, dal, pool_dp, pool_dp.ld, y, y.ld, bn.weight, st["mean"],
@@ -786,7 +831,7 @@ class Builder:
                                st["mean"], st["invstd"], st["scale"], st["shift"], part, y.M, C, 1 if act else 0, self.code,
                                nbytes=(2 + (am is not None)) * y.M * C * self.esz))
         sums = self.f32(2 * C)
-        need_pg = bn.weight.requires_grad
+        need_pg = self.param_grad(bn.weight)
         if need_pg:
             gref, gbeta = self.pgrad(bn.weight)
             bref, _ = self.pgrad(bn.bias)
@@ -805,7 +850,7 @@ class Builder:
         # The gradient of a conv bias that feeds a train-mode BatchNorm is exactly zero (sum_m dy = 0 because
         # sum_m xhat = 0); torch computes ~1e-9 of round-off there.  It is not computed: the slot in the flat
         # gradient buffer stays at its initial zero, the parameter is still registered as "has a gradient".
-        if bias is not None and bias.requires_grad and id(bias) not in self._grad_first:
+        if bias is not None and self.param_grad(bias) and id(bias) not in self._grad_first:
             self.pgrad(bias)
             self.zero_grad_params.append(bias)
         # an operand added AFTER the activation (recurrent block x + relu(bn(.))) receives the incoming gradient itself: the
@@ -878,7 +923,7 @@ class Builder:
         self.fwd.append(Launch("mi355_bn_act", y, y.ld, st["scale"], st["shift"], None, 0, None, None,
                                r, r.ld if r is not None else 0, a, a.ld, y.M, y.C, flags, self.code,
                                nbytes=(2 + (r is not None)) * y.M * y.C * self.esz))
-        a.needs_grad = y.needs_grad or bn.weight.requires_grad or (r is not None and r.needs_grad)
+        a.needs_grad = y.needs_grad or self.param_grad(bn.weight) or (r is not None and r.needs_grad)
         if act:
             self.acts.append(("relu", a) if post_add is None else ("relu_pre", y, st["scale"], st["shift"]))
         a._plain_bn_relu = bool(act and r is None and self.training)      # (maxpool(): its gradient may ride in this layer's backward)
@@ -905,7 +950,7 @@ class Builder:
         a = out if out is not None else self.new_tensor(x.N, x.H, x.W, x.C)
         self.fwd.append(Launch("mi355_bn_act", x, x.ld, st["scale"], st["shift"], None, 0, None, None, None, 0, a, a.ld,
                                x.M, x.C, 1 if act else 0, self.code))
-        a.needs_grad = x.needs_grad or bn.weight.requires_grad
+        a.needs_grad = x.needs_grad or self.param_grad(bn.weight)
 
         def rule():
             if not a.needs_grad:
@@ -952,13 +997,13 @@ class Builder:
         self.fwd.append(Launch("mi355_conv2d_igemm", x, wf, mod.bias, y, x.N, x.H, x.W, Ci, x.ld, Ho, Wo, Co, y.ld, k, k,
                                1, -1, 0, s, 0, 0, None, self.code, flops=flops, nbytes=nbytes,
                                tag=self.igemm_tag(x.N, x.H, x.W, Ci, Ho, Wo, Co, k, 1, -1, 0, s, 0)))
-        y.needs_grad = x.needs_grad or mod.weight.requires_grad
+        y.needs_grad = x.needs_grad or self.param_grad(mod.weight)
 
         def rule():
             if not y.needs_grad:
                 return
             dy = self.grad_of(y)
-            if mod.weight.requires_grad:
+            if self.param_grad(mod.weight):
                 # roles swap: the big tensor dy is gathered with stride-s addressing, x is the "dy" operand
                 splits = lib.mi355_conv2d_wgrad_splits(x.N, x.H, x.W, Co, Ci, k, k)
                 ws = self.ws_bytes(splits * Ci * k * k * Co * 4)
@@ -1102,7 +1147,7 @@ class Builder:
                                    sp["scale"], sp["shift"]))
         y = out if out is not None else self.new_tensor(x.N, x.H, x.W, x.C)
         self.fwd.append(Launch("mi355_gate_mul_fwd", x, x.ld, z, sp["scale"], sp["shift"], y, y.ld, M, x.C, self.code))
-        trainable = any(q.requires_grad for q in att.parameters())
+        trainable = any(self.param_grad(q) for q in att.parameters())
         y.needs_grad = x.needs_grad or g.needs_grad or trainable
 
         def rule():
@@ -1139,13 +1184,13 @@ class Builder:
                 sums = []
                 for q1, bn_, bias_ in ((1, bg, cg.bias), (2, bx, cx.bias)):
                     sm = self.f32(2 * F_int)
-                    need_pg = bn_.weight.requires_grad
+                    need_pg = self.param_grad(bn_.weight)
                     if need_pg:
                         gref_, gbeta_ = self.pgrad(bn_.weight)
                         bref_, _ = self.pgrad(bn_.bias)
                     self.bwd.append(Launch("mi355_bn_bwd_finalize_at", part3, nbf, 5, 0, q1, F_int, sm, gref_ if need_pg else None,
                                            bref_ if need_pg else None, gbeta_ if need_pg else 0.0))
-                    if bias_ is not None and bias_.requires_grad and id(bias_) not in self._grad_first:      # (see _bn_bwd)
+                    if bias_ is not None and self.param_grad(bias_) and id(bias_) not in self._grad_first:      # (see _bn_bwd)
                         self.pgrad(bias_)
                         self.zero_grad_params.append(bias_)
                     sums.append(sm)
@@ -1184,7 +1229,7 @@ class Builder:
         last = self.fwd[-1] if self.fwd else None
         fused = (FUSE_HEAD and K == 1 and x._plain_bn_relu and x._bn_src is not None and last is not None and last.name == "mi355_bn_act"
                  and last.args[10] is x and self.acts and self.acts[-1] == ("relu", x) and bool(lib.mi355_gate_psi_fwd_ok(C, self.code))
-                 and (x.needs_grad or not conv.weight.requires_grad))      # (the head's weight gradient comes out of the layer's backward passes)
+                 and (x.needs_grad or not self.param_grad(conv.weight)))      # (the head's weight gradient comes out of the layer's backward passes)
         if fused:
             # x = relu(bn(y)) is read by this convolution only: one pass over y computes it on the fly (mi355_gate_psi_fwd with one
             # normalised operand) — the activation is stored in neither direction (the backward recomputes it from y as well)
@@ -1197,7 +1242,7 @@ class Builder:
                 self.fwd.append(Launch("mi355_rowdot_fwd", x, x.ld, (conv.weight, k * C * 4), (conv.bias, k * 4) if conv.bias is not None else None,
                                        (z, k * HW * 4), None, M, C, HW, K, self.code))
         self.output = ("z", z, (x.N, K, x.H, x.W))
-        needs = x.needs_grad or conv.weight.requires_grad
+        needs = x.needs_grad or self.param_grad(conv.weight)
         if self.want_grad and needs:
             self.dout = self.f32(M * K)
 
@@ -1217,7 +1262,7 @@ class Builder:
                 part = self.ws_f32(nb * 2 * C)
                 self.bwd.append(Launch("mi355_rowdot_bwd", (self.dout, k * HW * 4), x, x.ld, (conv.weight, k * C * 4), dx,
                                        dx.ld if dx is not None else 0, part, M, C, 0, HW, K, 1 if k else 0, self.code))
-                if conv.weight.requires_grad:
+                if self.param_grad(conv.weight):
                     wref, wbeta = self.pgrad(conv.weight)
                     self.bwd.append(Launch("mi355_colsum_finalize", part, nb, 2, C, GRef(wref.tensor, wref.off + k * C * 4, wref.param),
                                            wbeta if k == 0 else 0.0))
@@ -1272,10 +1317,10 @@ class Builder:
         self.fwd.append(Launch("mi355_linear_fwd", v, lin.weight, lin.bias, y, v.B, v.F, O, 1 if relu else 0))
         if relu:
             self.acts.append(("relu_v", y))
-        y.needs_grad = v.needs_grad or lin.weight.requires_grad
+        y.needs_grad = v.needs_grad or self.param_grad(lin.weight)
         if is_output:
             self.output = ("v", y, (v.B, O))
-            if self.want_grad and y.needs_grad:
+            if self.recording and y.needs_grad:
                 self.dout = self.f32(v.B * O)
                 y._grad = V(self.dout, v.B, O)
 
@@ -1290,7 +1335,7 @@ class Builder:
                 dx = self.grad_of(v)
             dw = db = None
             beta = 0.0
-            if lin.weight.requires_grad:
+            if self.param_grad(lin.weight):
                 dw, beta = self.pgrad(lin.weight)
                 if lin.bias is not None:
                     db, _ = self.pgrad(lin.bias)
@@ -1427,8 +1472,20 @@ class Builder:
                 self.static_params = [e[0] for e in frozen]
             if live:
                 self.pre.append(pack_launch(live))
+        if self.cam is not None:
+            # Grad-CAM: one-hot seed of the explained class into dout, the head's backward down to the tap, the map
+            kind, y, _ = self.output
+            assert kind == "v" and self.dout is not None, "the CAM tap must feed the classifier head"
+            self.cam_target = self._alloc(y.B, torch.int32)
+            self.bwd.append(Launch("mi355_cam_seed", y, None, y.B, y.F, self.dout, self.cam_target))
         for r in reversed(self._rules):
             r()
+        if self.cam is not None:
+            t = self.cam
+            g = self.grad_of(t)
+            assert g._written, "the head's backward did not reach the CAM tap"
+            self.cam_lowres = self.f32(t.N * t.H * t.W)
+            self.bwd.append(Launch("mi355_gradcam", t, t.ld, g, g.ld, t.N, t.H * t.W, t.C, self.code, self.cam_lowres))
         assert not self._pending_wgrad, "a shared convolution's weight gradient is still waiting for an application's backward"
         # The side launches BEHIND the last main-stream launch of the backward (the first layer's weight gradient and its reduce)
         # have nothing left to overlap with: on the side stream they only put a cross-queue join (~50 us until the main queue sees the

@@ -81,7 +81,7 @@ class _ResNet(Net):
         for i in range(1, len(self.PLAN) + 1):
             for blk in getattr(self, f"layer{i}"):
                 t = blk.lower(g, t)
-        v = g.global_pool(t, is_max=True)
+        v = g.global_pool(g.cam_tap(t), is_max=True)         # (Grad-CAM target layer: layer4 output)
         g.head(self.fc, v)
 
 

@@ -86,7 +86,7 @@ class ResNet(Net):
         for i in range(1, 5):
             for blk in getattr(self, f"layer{i}"):
                 t = blk.lower(g, t)
-        v = g.global_pool(t, is_max=False)
+        v = g.global_pool(g.cam_tap(t), is_max=False)        # (Grad-CAM target layer: layer4 output)
         g.head(self.fc, v)
 
 

@@ -54,7 +54,7 @@ class _VGG(Net):
         self.classifier = Classifier(num_classes).classifier
 
     def build(self, g, x):
-        t = g.seq(self.features, x)
+        t = g.cam_tap(g.seq(self.features, x))             # (Grad-CAM target layer: the output of features)
         g.head(self.classifier, t)
 
 
@@ -89,7 +89,7 @@ class _VGG_BN(Net):
                                         nn.Linear(4096, num_classes))
 
     def build(self, g, x):
-        t = g.seq(self.features, x)
+        t = g.cam_tap(g.seq(self.features, x))             # (Grad-CAM target layer: the output of features)
         v = g.seq([self.avgpool], t)
         g.head(self.classifier, v)
 

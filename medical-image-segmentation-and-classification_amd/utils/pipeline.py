@@ -7,9 +7,10 @@
 The reference handles one PIL image per call and synchronises after every model; here the only host
 round-trip is the number of kept samples (it sizes the segmentation launch).  The compacted batch is
 padded to a multiple of ``bucket`` so that at most B / bucket launch plans ever exist per image size.
-Image decoding / resizing / normalisation (pipeline.py:196-215, 381-390) and the red overlay (:399-413)
-are host-side presentation code outside the hot path: ``predict`` takes the already normalised tensor
-(``val_transform`` output) and returns the masks."""
+``predict`` takes the already normalised tensor (``val_transform`` output) and returns the masks (with ``explain=True``
+also the Grad-CAM map of every sample's predicted class, utils/explain.py).  ``process_images`` is ``process_image``'s
+per-file result — the red overlay at the file's own size (:399-413, mi355_overlay_mask) and the analysis text (:391-417) —
+for a list of PNG files, run as one batch."""
 from __future__ import annotations
 
 import torch
@@ -29,13 +30,21 @@ class JointPipeline:
         self.segmentation_model = None if segmentation_model is None else segmentation_model.to(self.device).eval()
 
     @torch.no_grad()
-    def predict(self, x):
+    def predict(self, x, explain=False):
         """x: [B,3,H,W] normalised float (B <= 1024).  Returns a dict of device tensors:
         ``pred`` int32 [B] class index, ``confidence`` float [B] in percent, ``masks`` uint8 [B,H,W] (0 / 255; all zero
-        where no segmentation ran), ``segmented`` bool [B]."""
+        where no segmentation ran), ``segmented`` bool [B].  ``explain``: also ``cam`` float32 [B,H,W] (and ``cam_lowres`` at
+        the feature-map size), the Grad-CAM of each sample's predicted class; the logits then come from the classifier's explain
+        plan, whose forward is the eval forward: every other output is the same, bit for bit."""
         x = x.to(self.device, dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
-        logits = self.classification_model(x).float().contiguous()
+        cams = None
+        if explain:
+            from utils.explain import GradCAM
+            cams = GradCAM(self.classification_model)(x)
+            logits = cams["logits"].float().contiguous()
+        else:
+            logits = self.classification_model(x).float().contiguous()
         pred = torch.empty(B, dtype=torch.int32, device=self.device)
         conf = torch.empty(B, dtype=torch.float32, device=self.device)
         kept = torch.empty(B + self.bucket, dtype=torch.int32, device=self.device)
@@ -56,7 +65,10 @@ class JointPipeline:
             lib.mi355_mask_scatter(z.float().contiguous(), kept, n, H * W, 0.5, masks)
         elif self.segmentation_model is None:
             segmented = torch.zeros_like(segmented)
-        return {"pred": pred, "confidence": conf, "masks": masks, "segmented": segmented}
+        out = {"pred": pred, "confidence": conf, "masks": masks, "segmented": segmented}
+        if cams is not None:
+            out["cam"], out["cam_lowres"] = cams["cam"], cams["cam_lowres"]
+        return out
 
     def process_files(self, paths, size=256, threads=8):
         """PNG files -> the reference's per-image results.  The reference opens each file with PIL, applies ``A.Resize(256, 256)`` +
@@ -74,3 +86,51 @@ class JointPipeline:
         pred, conf, seg = r["pred"].cpu(), r["confidence"].cpu(), r["segmented"].cpu()
         masks = r["masks"].cpu()
         return [(self.classes[int(pred[i])], float(conf[i]), masks[i] if bool(seg[i]) else None) for i in range(len(pred))]
+
+    def process_images(self, paths, overlay_opacity=0.5, explain=False, size=256, threads=8, heatmap_alpha=0.4):
+        """PNG files -> one ``process_image`` result per file (pipeline.py:359-418): ``(prediction, confidence, output_img,
+        analysis_text)``.  ``output_img`` is a numpy uint8 RGB image at the file's own size — the red overlay of the segmentation
+        mask — for a "COVID" call with a segmentation model, else None, as in the reference.  ``explain``: a fifth element, the
+        Grad-CAM overlay (utils/explain.py overlay_heatmap, weight ``heatmap_alpha``) of the predicted class at the file's size.
+        Files of several sizes are decoded per size; all of them are classified / segmented as one batch."""
+        from utils.dataset import decode_batch, png_size, read_files
+        from utils.explain import overlay_heatmap, overlay_mask, resize_bilinear
+        from utils.gpu_transforms import SegBatchTransform
+        paths = list(paths)
+        bufs = read_files(paths)
+        groups = {}
+        for i, b in enumerate(bufs):
+            groups.setdefault(png_size(b), []).append(i)
+        tf = SegBatchTransform(size, train=False, device=self.device)
+        order, imgs, xs = [], [], []
+        for idx in groups.values():
+            im = decode_batch([bufs[i] for i in idx], 3, threads, names=[paths[i] for i in idx]).to(self.device, non_blocking=True)
+            order.append(idx)
+            imgs.append(im)
+            xs.append(tf(im))
+        r = self.predict(torch.cat(xs) if len(xs) > 1 else xs[0], explain=explain)
+        pred, conf = r["pred"].cpu(), r["confidence"].cpu()
+        positive = self.classes[self.keep]
+        results = [None] * len(paths)
+        row = 0
+        for idx, im in zip(order, imgs):
+            n, H0, W0, _ = im.shape
+            red = overlay_mask(im, r["masks"][row:row + n], overlay_opacity).cpu().numpy() if self.segmentation_model is not None else None
+            heat = None
+            if explain:
+                heat = overlay_heatmap(im, resize_bilinear(r["cam_lowres"][row:row + n].contiguous(), (H0, W0)), heatmap_alpha).cpu().numpy()
+            for j, i in enumerate(idx):
+                prediction, confidence = self.classes[int(pred[row + j])], float(conf[row + j])
+                output_img = None
+                text = f"Diagnosis: {prediction}\nConfidence: {confidence:.2f}%\n"
+                if prediction != positive:
+                    text += ("\nRecommendation: Consult a medical professional for final diagnosis. The model suggests no severe "
+                             "COVID-19 pathology.")
+                elif red is not None:
+                    output_img = red[j]
+                    text += "\nInfection areas have been highlighted in red (segmentation model)."
+                else:
+                    text += "\nWARNING: Segmentation model failed to load. Cannot highlight infection areas."
+                results[i] = (prediction, confidence, output_img, text) + ((heat[j],) if explain else ())
+            row += n
+        return results
