@@ -340,6 +340,24 @@ int mi355_bce_logits(const float* z, const float* t, float* loss, float* dz, con
 /* CrossEntropyLoss(label_smoothing): loss[0], dz[B][C]. */
 int mi355_ce_smooth(const float* z, const int64_t* y, float* loss, float* dz, const float* gscale, int B,
                     int C, float smoothing, mi355_stream_t s);
+/* Dice / BCE + Dice on fp32 logits and targets [B][per] (the reference's DiceLoss / CombinedLoss,
+ * utils/clip_seg_finetuner.py:40-74).  p = sigmoid(z), I = sum p t, P = sum p, T = sum t, D = P + T + smooth:
+ *   loss[0] = bce_weight * mean(BCEWithLogits(z, t)) + dice_weight * (1 - (2 I + smooth) / D)
+ * with the sums over the whole batch (per_sample = 0, the reference) or per image, the B Dice terms averaged
+ * (per_sample = 1; the BCE term is the same).  Deterministic: no floating-point atomics, every fold in a fixed order.
+ *   mi355_seg_loss_rows: rows of four floats `partial` must hold (16-byte aligned); a function of (B, per) alone.
+ *   mi355_seg_loss_fwd:  one pass over z and t (16-byte accesses when per % 4 == 0 and z, t are 16-byte aligned), a
+ *     one-workgroup finalize in double; leaves loss[0] and, in state[2 b], state[2 b + 1], the pair (a_b, c_b) of
+ *     sample b: a = dice_weight 2 / D, c = dice_weight (2 I + smooth) / D^2 (per_sample: its own sums, both / B).
+ *   mi355_seg_loss_bwd:  one pass, dz_i = gscale[0] * (bce_weight (p_i - t_i) / (B per) - (a_b t_i - c_b) p_i (1 - p_i))
+ *     from the `state` the forward left (same B, per, bce_weight); gscale = upstream gradient x loss scale on the
+ *     device, NULL = 1.  It does not recompute the loss.
+ * B <= 65535; weights and smooth >= 0 (smooth = 0 with an all-zero target divides by sum p alone). */
+int mi355_seg_loss_rows(int B, long long per);
+int mi355_seg_loss_fwd(const float* z, const float* t, int B, long long per, float bce_weight, float dice_weight,
+                       float smooth, int per_sample, float* partial, float* state, float* loss, mi355_stream_t s);
+int mi355_seg_loss_bwd(const float* z, const float* t, int B, long long per, float bce_weight, const float* state,
+                       const float* gscale, float* dz, mi355_stream_t s);
 
 /* ---- optimiser on flat fp32 buffers (utils/helpers.py:251,304,332-336) ---------------------- */
 /* sumsq partials of a flat gradient buffer; nblocks = mi355_rowreduce_blocks(n). */

@@ -114,12 +114,15 @@ def _make_optimizer(params, lr):
     return moptim.AdamW(params, lr=lr, weight_decay=5e-4)
 
 
-def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False, cls_head_name=None):
+def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False, cls_head_name=None, criterion=None):
     device = torch.device(device)
     model = model.to(device)
     if hasattr(model, "engine"):
         model.engine._check_storage()                 # flat fp32 parameter / gradient buffers
-    criterion = mnn.BCEWithLogitsLoss() if seg else mnn.CrossEntropyLoss(label_smoothing=0.1)
+    # criterion: a loss module of mi355.nn (mnn.DiceLoss(), mnn.CombinedLoss(), ...) for the training AND the validation loss;
+    # None = the reference's choice
+    if criterion is None:
+        criterion = mnn.BCEWithLogitsLoss() if seg else mnn.CrossEntropyLoss(label_smoothing=0.1)
     STAGE1 = 5
 
     # data parallel (module docstring): the reference's loop on this rank's batches, gradients averaged over ranks

@@ -7,6 +7,7 @@ out of scope); this driver keeps its protocol — classification 
 defaults to synthetic 256x256 batches so that it runs anywhere:
 
     python utils/trainer.py --task seg --model attentionunet --epochs 2 --samples 64
+    python utils/trainer.py --task seg --model r2attunet --seg-loss bce_dice --bce-weight 0.5 --dice-weight 0.5
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -54,7 +55,7 @@ def make_loader(ds, bs, shuffle):
     return DataLoader(ds, batch_size=bs, shuffle=shuffle, num_workers=0, pin_memory=True, drop_last=False)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=["cls", "seg", "both"], default="seg")
     ap.add_argument("--model", default=None, help="one model name; default: every model of the task (trainer.py:163-168)")
@@ -64,7 +65,27 @@ def main():
     ap.add_argument("--size", type=int, default=IMG_SIZE)
     ap.add_argument("--save-dir", default="weights")
     ap.add_argument("--data-root", default=None, help="dataset directory in the reference's layout; default: synthetic batches")
-    args = ap.parse_args()
+    ap.add_argument("--seg-loss", choices=["bce", "dice", "bce_dice"], default="bce",
+                    help="segmentation loss: BCEWithLogits (the reference's train()), Dice, or bce_weight * BCE + dice_weight * Dice "
+                         "(the reference's DiceLoss / CombinedLoss, clip_seg_finetuner.py:40-74)")
+    ap.add_argument("--bce-weight", type=float, default=0.5, help="bce_dice: weight of the BCE term")
+    ap.add_argument("--dice-weight", type=float, default=0.5, help="bce_dice: weight of the Dice term")
+    ap.add_argument("--dice-per-sample", action="store_true", help="Dice term per image, averaged over the batch (default: over the whole batch)")
+    return ap
+
+
+def seg_criterion(args):
+    """The loss module --seg-loss asks for; None = train()'s own default (BCEWithLogits)."""
+    if args.seg_loss == "bce":
+        return None
+    from mi355 import nn as mnn
+    if args.seg_loss == "dice":
+        return mnn.DiceLoss(per_sample=args.dice_per_sample)
+    return mnn.CombinedLoss(args.bce_weight, args.dice_weight, per_sample=args.dice_per_sample)
+
+
+def main():
+    args = build_parser().parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("the MI355X path needs a GPU (no CPU fallback)")
     # one process per GPU under torch.distributed.run: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the launcher
@@ -118,7 +139,8 @@ def main():
                              seg=False, cls_head_name=head)
             else:
                 model = get_seg_model(name)
-                best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True)
+                best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True,
+                             criterion=seg_criterion(args))
             results[(task, name)] = best
     say("\n===== SUMMARY =====")
     for (task, name), best in results.items():
