@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "conv3x3_tile.hpp"
 
 // ---- patch-row register window -------------------------------------------------------------------------------------
 // Wave tile = 128 pixels
@@ -64,14 +65,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_rw_kernel(const ConvArgs 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, c4 = lane >> 4;
   const int wm = wave / WN, wn = wave % WN;
-  const int NT = a.Co / BN, TXN = a.Wo / TW, TYN = a.Ho / TH;
-  const int bid = xcd_tile(blockIdx.x, gridDim.x);
-  int t = bid;
-  const int nt = t % NT; t /= NT;
-  const int tx = t % TXN; t /= TXN;
-  const int ty = t % TYN;
-  const int n = t / TYN;
-  const int y0 = ty * TH, x0 = tx * TW, n0 = nt * BN;
+  const HaloTile tile = halo_tile<TH, TW, BN>(a);
+  const int n = tile.n, y0 = tile.y0, x0 = tile.x0, n0 = tile.n0;
   const T* __restrict__ in = reinterpret_cast<const T*>(a.in);
   const T* __restrict__ wk = reinterpret_cast<const T*>(a.wk);
   const char* zero = reinterpret_cast<const char*>(g_zero_page);
@@ -107,9 +102,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_rw_kernel(const ConvArgs 
   const size_t wrow = (size_t)9 * a.Ci;
   const int brow = wave * 16 + lrow;
   const bufdesc_t desc_w = make_buf(wk + (size_t)n0 * wrow), desc_none = make_buf(wk, false);
-  const unsigned b_off = (unsigned)(((size_t)brow * wrow + (slot ^ (((brow >> 2) & 1) << 1)) * EPC) * 2);
+  const unsigned b_off = (unsigned)(weight_row_offset<T>(brow, wrow, slot) * 2);
   auto issue_stage_piece = [&](int stage, int pw, int c0, int ph) {      // c0 < 0: nothing left to fetch (zeros into a dead slot)
-    const int tap = flip ? (2 - ph) * 3 + (2 - pw) : ph * 3 + pw;
+    const int tap = tap_index(flip, ph, pw);
     dma16_buf(c0 >= 0 ? desc_w : desc_none, b_off, (unsigned)(tap * a.Ci + c0) * 2u, lds0 + 2 * PATCH_BYTES + stage * STAGE + wave * 1024 + ph * SLAB);
   };
 
@@ -219,17 +214,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_rw_kernel(const ConvArgs 
   }
   wait_vmcnt<0>();                                   // (the zero-fill pieces of the last two steps)
 
-  // ---- epilogue --------------------------------------------------------------------------------------------------------
-  // The MFMAs ran with the weight fragment as the A operand, so a lane holds, per 16x16 block, FOUR CONSECUTIVE CHANNELS
-  // (4*c4 .. +3) of ONE pixel (l16): bias / ReLU / rounding happen once per value in registers, a block is staged with ONE
-  // 8-byte LDS write per lane (conflict-free at the 144-B row pitch), and the tile leaves as 16-byte row-contiguous stores
-  // (whole 128-B lines; 8-byte stores straight from the registers were measured: 4x the line accesses, -10 %).
+  // ---- epilogue: the staged C tile (contract: conv3x3_tile.hpp); the sums are folded over the two wave rows through LDS -------
   T* __restrict__ out = reinterpret_cast<T*>(a.out);
   struct alignas(8) Pack4 { T v[4]; };
   float* const red = reinterpret_cast<float*>(lds + Cfg::C_BYTES);      // [WM][2][BN] behind the C tile
-  // ReLU and the statistics are workgroup-uniform switches: four straight-line variants instead of 64 dead v_max / a test per
-  // block.  Statistics are of the ROUNDED outputs, summed two channels at a time (packed fp32 adds / fmas), folded over
-  // the 16 pixel lanes of a row with DPP adds (no LDS traffic), then over the two wave rows through LDS.
   auto finish = [&](auto relu_tag, auto stats_tag) {
     constexpr bool RELU = decltype(relu_tag)::value, STATS = decltype(stats_tag)::value;
     f32x2 sm[NB][2], sq[NB][2];
@@ -276,16 +264,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_rw_kernel(const ConvArgs 
     if (a.relu) finish(Yes{}, No{}); else finish(No{}, No{});
   }
   __syncthreads();
-  if (a.stats && tid < 2 * BN) {
-    const int q = tid / BN, c = tid - q * BN;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < WM; ++w) v += red[(w * 2 + q) * BN + c];
-    a.stats[((size_t)(bid / NT) * 2 + q) * a.Co + n0 + c] = v;
-  }
+  fold_tile_stats<WM, BN>(a, red, tid, tile);
   constexpr int CPRC = BN / EPC;
-  if (a.pool2) {       // gradient of a fused nearest x2 up-sampling: the four outputs of a 2x2 group are summed (fp32, from the
-                       // ROUNDED tile values, as the separate mi355_upsample2_bwd pass did) into the half-resolution tensor
+  if (a.pool2) {
     const int Ho2 = a.Ho >> 1, Wo2 = a.Wo >> 1;
     for (int id = tid; id < (BM / 4) * CPRC; id += 256) {
       const int g = id / CPRC, c = id - g * CPRC;
@@ -347,14 +328,5 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_rw_kernel(const ConvArgs 
 template <typename T, int TH, int TW>
 static int launch_halo_rw(const ConvArgs& a, hipStream_t s) {
   const int grid = a.N * (a.Ho / TH) * (a.Wo / TW) * (a.Co / 64);
-  constexpr int lds_bytes = HaloRwCfg<TH, TW>::LDS_BYTES;
-  // once per process and kernel variant; a function-local static is initialised exactly once even when two threads launch
-  // concurrently (forward on the main thread, backward on the autograd worker)
-  static const hipError_t configured = hipFuncSetAttribute((const void*)conv3x3_halo_rw_kernel<T, TH, TW>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (configured != hipSuccess)
-    MI355_FAIL((int)configured, "conv3x3_halo_rw: cannot reserve %d B of LDS: %s", lds_bytes, hipGetErrorString(configured));
-  hipLaunchKernelGGL((conv3x3_halo_rw_kernel<T, TH, TW>), dim3(grid), dim3(256), lds_bytes, s, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return launch_with_lds<conv3x3_halo_rw_kernel<T, TH, TW>, HaloRwCfg<TH, TW>::LDS_BYTES>("conv3x3_halo_rw", grid, 256, s, a);
 }

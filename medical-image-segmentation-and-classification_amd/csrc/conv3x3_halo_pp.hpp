@@ -21,14 +21,15 @@
 //                 (no-DMA ceiling 1885 TFLOP/s on 32x32x1024->512, 1482 with the unbalanced schedule).  Counted vmcnt waits at
 //                 the end of every wave's (2s+1)-phase keep exactly the youngest issues in flight: this step's stage and patch
 //                 pieces and the previous step's patch pieces (stage pieces are issued first)
-//   epilogue    : as conv3x3_halo.hpp (a lane owns four consecutive channels of a pixel; LDS-staged 16-byte row stores), one
-//                 C tile per half; half 0 stages its tile while half 1 runs its last matrix phase
+//   epilogue    : the staged C tile of conv3x3_tile.hpp, one C tile per half; half 0 stages its tile while half 1 runs its
+//                 last matrix phase
 // Everything else (patch / slab images, swizzles, fragment maps, tap mirroring for the data gradient, x2 up-sampling in the
-// gather, ReLU / statistics / 2x2-sum epilogues) is that kernel's.
+// gather) is conv3x3_halo.hpp's.
 #pragma once
 #include <type_traits>
 
 #include "common.hpp"
+#include "conv3x3_tile.hpp"
 
 struct HaloPpCfg {
   static constexpr int TH = 16, TW = 32, HTH = 8, BN = 64;
@@ -67,14 +68,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp_kernel(const ConvArgs a) 
   const int half = wave >> 2, w4 = wave & 3;
   const int l16 = lane & 15, c4 = lane >> 4;
   const int wm = w4 / WN, wn = w4 % WN;
-  const int NT = a.Co / BN, TXN = a.Wo / TW, TYN = a.Ho / TH;
-  const int bid = xcd_tile(blockIdx.x, gridDim.x);
-  int t = bid;
-  const int nt = t % NT; t /= NT;
-  const int tx = t % TXN; t /= TXN;
-  const int ty = t % TYN;
-  const int n = t / TYN;
-  const int y0 = ty * TH, x0 = tx * TW, n0 = nt * BN;
+  const HaloTile tile = halo_tile<TH, TW, BN>(a);
+  const int n = tile.n, y0 = tile.y0, x0 = tile.x0, n0 = tile.n0;
   const T* __restrict__ in = reinterpret_cast<const T*>(a.in);
   const T* __restrict__ wk = reinterpret_cast<const T*>(a.wk);
   const char* zero = reinterpret_cast<const char*>(g_zero_page);
@@ -107,9 +102,11 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp_kernel(const ConvArgs a) 
   // w4 brings rows [16 w4, +16) of slabs 0 and 2, half 1's wave w4 the same rows of slab 1.
   const size_t wrow = (size_t)9 * a.Ci;
   const int brow = w4 * 16 + lrow;
+  // (not weight_row_offset(): the rows are addressed from wk, not from the channel tile's base, and n0 * wrow + offset costs
+  // six more instructions than (n0 + brow) * wrow)
   const T* const b_src = wk + (size_t)(n0 + brow) * wrow + (slot ^ (((brow >> 2) & 1) << 1)) * EPC;
   auto issue_stage_piece = [&](int stage, int pw, int c0, int ph) __attribute__((always_inline)) {      // c0 < 0: nothing left to fetch (zeros into a dead slot)
-    const int tap = flip ? (2 - ph) * 3 + (2 - pw) : ph * 3 + pw;
+    const int tap = tap_index(flip, ph, pw);
     const char* p = c0 >= 0 ? reinterpret_cast<const char*>(b_src + (size_t)tap * a.Ci + c0) : zero + slot * 16;
     dma16(p, lds_addr(bring + stage * STAGE + w4 * 1024 + ph * SLAB));
   };
@@ -334,13 +331,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp_kernel(const ConvArgs a) 
   __builtin_amdgcn_s_barrier();
   if (half == 1) finish_any();
   __syncthreads();
-  if (a.stats && tid < 2 * BN) {
-    const int q = tid / BN, c = tid - q * BN;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += red[(w * 2 + q) * BN + c];
-    a.stats[((size_t)(bid / NT) * 2 + q) * a.Co + n0 + c] = v;
-  }
+  fold_tile_stats<4, BN>(a, red, tid, tile);
   constexpr int CPRC = BN / EPC;
   constexpr int BM = TH * TW;                 // 512 tile pixels: tile row r lives in C tile r / 256 at row r % 256
   if (a.pool2) {
@@ -391,12 +382,5 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp_kernel(const ConvArgs a) 
 template <typename T>
 static int launch_halo_pp(const ConvArgs& a, hipStream_t s) {
   const int grid = a.N * (a.Ho / HaloPpCfg::TH) * (a.Wo / HaloPpCfg::TW) * (a.Co / 64);
-  constexpr int lds_bytes = HaloPpCfg::LDS_BYTES;
-  static const hipError_t configured =
-      hipFuncSetAttribute((const void*)conv3x3_halo_pp_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (configured != hipSuccess)
-    MI355_FAIL((int)configured, "conv3x3_halo_pp: cannot reserve %d B of LDS: %s", lds_bytes, hipGetErrorString(configured));
-  hipLaunchKernelGGL((conv3x3_halo_pp_kernel<T>), dim3(grid), dim3(512), lds_bytes, s, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return launch_with_lds<conv3x3_halo_pp_kernel<T>, HaloPpCfg::LDS_BYTES>("conv3x3_halo_pp", grid, 512, s, a);
 }

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "conv3x3_tile.hpp"
 
 struct HaloPp128Cfg {
   static constexpr int TH = 16, TW = 32, HTH = 8, BN = 128;
@@ -65,14 +66,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp128_kernel(const ConvArgs 
   const int half = wave >> 2, w4 = wave & 3;
   const int l16 = lane & 15, c4 = lane >> 4;
   const int wm = w4 / WN, wn = w4 % WN;
-  const int NT = a.Co / BN, TXN = a.Wo / TW, TYN = a.Ho / TH;
-  const int bid = xcd_tile(blockIdx.x, gridDim.x);
-  int t = bid;
-  const int nt = t % NT; t /= NT;
-  const int tx = t % TXN; t /= TXN;
-  const int ty = t % TYN;
-  const int n = t / TYN;
-  const int y0 = ty * TH, x0 = tx * TW, n0 = nt * BN;
+  const HaloTile tile = halo_tile<TH, TW, BN>(a);
+  const int n = tile.n, y0 = tile.y0, x0 = tile.x0, n0 = tile.n0;
   const T* __restrict__ in = reinterpret_cast<const T*>(a.in);
   const T* __restrict__ wk = reinterpret_cast<const T*>(a.wk);
   const char* zero = reinterpret_cast<const char*>(g_zero_page);
@@ -108,9 +103,9 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp128_kernel(const ConvArgs 
   const size_t wrow = (size_t)9 * a.Ci;
   const int brow = wave * 16 + lrow;
   const T* const wk0 = wk + (size_t)n0 * wrow;                                            // wave-uniform
-  const unsigned b_off = (unsigned)(((size_t)brow * wrow + (slot ^ (((brow >> 2) & 1) << 1)) * EPC) * 2);
+  const unsigned b_off = (unsigned)(weight_row_offset<T>(brow, wrow, slot) * 2);
   auto issue_stage_piece = [&](int stage, int pw, int c0, int ph) __attribute__((always_inline)) {
-    const int tap = flip ? (2 - ph) * 3 + (2 - pw) : ph * 3 + pw;
+    const int tap = tap_index(flip, ph, pw);
     dma16_sv_m0(wk0 + (size_t)tap * a.Ci + c0, b_off, lds0 + Cfg::NPB * PATCH_BYTES + stage * STAGE + wave * 1024 + ph * SLAB);
   };
   auto issue_stage = [&](int stage, int pw, int c0) __attribute__((always_inline)) {
@@ -355,13 +350,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp128_kernel(const ConvArgs 
   };
   finish_any();
   __syncthreads();
-  if (a.stats && tid < 2 * BN) {
-    const int q = tid / BN, c = tid - q * BN;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += red[(w * 2 + q) * BN + c];
-    a.stats[((size_t)(bid / NT) * 2 + q) * a.Co + n0 + c] = v;
-  }
+  fold_tile_stats<4, BN>(a, red, tid, tile);
   constexpr int CPRC = BN / EPC;
   constexpr int BM = TH * TW;                 // 512 tile pixels: tile row r lives in C tile r / 256 at row r % 256
   if (a.pool2) {
@@ -395,30 +384,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp128_kernel(const ConvArgs 
     }
     return;
   }
-#ifdef PP128_ACC_BATCH      // (A/B: all old values of the accumulate epilogue before the first store, as in the four-wave kernel)
-  constexpr int NST = BM * CPRC / 512;
-  static_assert(NST * 512 == BM * CPRC, "whole store rounds");
-  if (a.accumulate) {
-    Vec16<T> old[NST];
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int id = tid + it * 512, row = id / CPRC, c = id - row * CPRC;
-      const int py = row / TW, px = row - py * TW;
-      old[it] = ld16<T>(out + ((size_t)(n * a.Ho + y0 + py) * a.Wo + x0 + px) * a.ldo + n0 + c * EPC);
-    }
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int id = tid + it * 512, row = id / CPRC, c = id - row * CPRC;
-      const int py = row / TW, px = row - py * TW;
-      T* p = out + ((size_t)(n * a.Ho + y0 + py) * a.Wo + x0 + px) * a.ldo + n0 + c * EPC;
-      Vec16<T> v = *reinterpret_cast<const Vec16<T>*>(lds + (row / HBM) * Cfg::C_BYTES + (row % HBM) * C_PITCH + c * 16);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) v.v[e] = from_f32<T>(to_f32<T>(v.v[e]) + to_f32<T>(old[it].v[e]));
-      st16<T>(p, v);
-    }
-    return;
-  }
-#endif
   for (int id = tid; id < BM * CPRC; id += 512) {
     const int row = id / CPRC, c = id - row * CPRC;
     const int py = row / TW, px = row - py * TW;
@@ -436,12 +401,5 @@ __global__ __launch_bounds__(512) void conv3x3_halo_pp128_kernel(const ConvArgs 
 template <typename T>
 static int launch_halo_pp128(const ConvArgs& a, hipStream_t s) {
   const int grid = a.N * (a.Ho / HaloPp128Cfg::TH) * (a.Wo / HaloPp128Cfg::TW) * (a.Co / HaloPp128Cfg::BN);
-  constexpr int lds_bytes = HaloPp128Cfg::LDS_BYTES;
-  static const hipError_t configured =
-      hipFuncSetAttribute((const void*)conv3x3_halo_pp128_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (configured != hipSuccess)
-    MI355_FAIL((int)configured, "conv3x3_halo_pp128: cannot reserve %d B of LDS: %s", lds_bytes, hipGetErrorString(configured));
-  hipLaunchKernelGGL((conv3x3_halo_pp128_kernel<T>), dim3(grid), dim3(512), lds_bytes, s, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return launch_with_lds<conv3x3_halo_pp128_kernel<T>, HaloPp128Cfg::LDS_BYTES>("conv3x3_halo_pp128", grid, 512, s, a);
 }

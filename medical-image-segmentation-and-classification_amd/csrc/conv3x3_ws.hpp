@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "conv3x3_tile.hpp"
 
 template <int CI_, int TH_> struct WsCfg {
   static constexpr int TH = TH_, TW = 32, BN = 64, CI = CI_, NS = CI_ / 32;
@@ -154,32 +155,27 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ws_kernel(const ConvArgs a, co
   // same four channels) — ONE partial row per workgroup behind the loop (row kk: mi355_conv2d_igemm_stat_rows == groups), not one
   // per tile: 512 rows instead of 8192 at 256 x 256 x 32 images (no pre-fold launch, a 16 x smaller fold)
   f32x2 wsm[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, wsq[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}};
-  for (int sp = sp_begin; sp < sp_end; ++sp) {
-    // tiles in COLUMN order (ty fastest): consecutive tiles of a workgroup's range are vertical neighbours, so the two halo rows a
-    // tile shares with its predecessor were fetched one tile ago and are still in the XCD's L2 (-DWS_ROW_ORDER: tx fastest, A/B)
-    int t = sp;
+  // tiles in COLUMN order (ty fastest): consecutive tiles of a workgroup's range are vertical neighbours, so the two halo rows a
+  // tile shares with its predecessor were fetched one tile ago and are still in the XCD's L2 (-DWS_ROW_ORDER: tx fastest, A/B)
+  auto tile_of = [&](int sp, int& n, int& ty, int& tx) __attribute__((always_inline)) {
 #ifdef WS_ROW_ORDER
-    const int tx = t % TXN; t /= TXN;
-    const int ty = t % TYN;
-    const int n = t / TYN;
+    tx = sp % TXN; sp /= TXN;
+    ty = sp % TYN;
+    n = sp / TYN;
 #else
-    const int ty = t % TYN; t /= TYN;
-    const int tx = t % TXN;
-    const int n = t / TXN;
+    ty = sp % TYN; sp /= TYN;
+    tx = sp % TXN;
+    n = sp / TXN;
 #endif
+  };
+  for (int sp = sp_begin; sp < sp_end; ++sp) {
+    int n, ty, tx;
+    tile_of(sp, n, ty, tx);
     const int y0 = ty * TH, x0 = tx * TW;
     // descriptor + lane offsets of a tile's patch
     auto patch_of = [&](int sp2, bufdesc_t& desc, unsigned (&off)[P_IT]) __attribute__((always_inline)) {
-      int t2 = sp2;
-#ifdef WS_ROW_ORDER
-      const int tx2 = t2 % TXN; t2 /= TXN;
-      const int ty2 = t2 % TYN;
-      const int n2 = t2 / TYN;
-#else
-      const int ty2 = t2 % TYN; t2 /= TYN;
-      const int tx2 = t2 % TXN;
-      const int n2 = t2 / TXN;
-#endif
+      int n2, ty2, tx2;
+      tile_of(sp2, n2, ty2, tx2);
       const int yy0 = ty2 * TH - 1, xx0 = tx2 * TW - 1;                  // logical coordinates of the patch origin
       const long long org = ((long long)n2 * a.Hi * a.Wi + (long long)(yy0 >> a.up) * a.Wi + (xx0 >> a.up)) * a.ldi;   // (floor shifts)
       desc = make_buf(in + org);
@@ -276,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ws_kernel(const ConvArgs a, co
     wait_vmcnt<(NS - 2) * P_IT>();                                       // the next tile's slab 0 has landed (behind it: its slabs 1 .. NS - 2)
     __builtin_amdgcn_s_barrier();                                        // the last slab's buffer is free
 
-    // ---- epilogue: a lane holds, per block, FOUR CONSECUTIVE CHANNELS (16 wave + 4 c4 .. + 3) of pixel (row, 16 xb + l16) ----
+    // ---- epilogue: the staged C tile (contract: conv3x3_tile.hpp); channels 16 wave + 4 c4 .. + 3 of pixel (row, 16 xb + l16) ----
     unsigned char* const cst = lds + NS * SLAB;
     struct alignas(8) Pack4 { T v[4]; };
     auto finish = [&](auto relu_tag, auto stats_tag) __attribute__((always_inline)) {
@@ -312,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ws_kernel(const ConvArgs a, co
     __builtin_amdgcn_s_waitcnt(0xc07f);                                  // lgkmcnt(0): the staging writes are done
     __builtin_amdgcn_s_barrier();
     constexpr int CPRC = BN / EPC;
-    if (a.pool2) {       // gradient of a fused nearest x2 up-sampling: 2x2 output groups summed into the half-resolution tensor
+    if (a.pool2) {
       const int Ho2 = a.Ho >> 1, Wo2 = a.Wo >> 1;
       for (int id = tid; id < (BM / 4) * CPRC; id += 256) {
         const int g = id / CPRC, c = id - g * CPRC;
@@ -405,12 +401,5 @@ static int launch_ws(const ConvArgs& a, hipStream_t s, int cus) {
   const int S = a.N * (a.Ho / TH) * (a.Wo / 32);
   const int groups = ws_groups(a.N, a.Ho, a.Wo, a.Co, TH, cus);
   if (groups < 8) MI355_FAIL(MI355_ERR_ARG, "conv3x3_ws: %d spatial tiles are too few for the persistent kernel", S);
-  constexpr int lds_bytes = WsCfg<CI, TH>::LDS_BYTES;
-  static const hipError_t configured = hipFuncSetAttribute((const void*)conv3x3_ws_kernel<T, CI, TH>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (configured != hipSuccess)
-    MI355_FAIL((int)configured, "conv3x3_ws: cannot reserve %d B of LDS: %s", lds_bytes, hipGetErrorString(configured));
-  hipLaunchKernelGGL((conv3x3_ws_kernel<T, CI, TH>), dim3(groups * NT), dim3(256), lds_bytes, s, a, groups);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return launch_with_lds<conv3x3_ws_kernel<T, CI, TH>, WsCfg<CI, TH>::LDS_BYTES>("conv3x3_ws", groups * NT, 256, s, a, groups);
 }

@@ -34,17 +34,17 @@ _FMT = {torch.bfloat16: (7, -126), torch.float16: (10, -14), torch.float32: (23,
 
 # ---- epilogue rounding models -----------------------------------------------------------------------------------------------
 # Read from the kernels' epilogues (csrc/); every 2-byte variant rounds the same way, the fp32 generic kernel keeps fp32 throughout:
-#   "round"    y = R(relu?(acc + bias))                  one rounding.  conv3x3_halo.hpp:247 / conv3x3_halo_pp.hpp:300 /
-#              conv3x3_ws.hpp:289 (bias = the first MFMA's C operand); conv3x3_halo_pp128.hpp:322-323, conv_gemm256.hpp:185-186,
+#   "round"    y = R(relu?(acc + bias))                  one rounding.  conv3x3_halo.hpp:235 / conv3x3_halo_pp.hpp:297 /
+#              conv3x3_ws.hpp:285 (bias = the first MFMA's C operand); conv3x3_halo_pp128.hpp:317-318, conv_gemm256.hpp:185-186,
 #              conv1x1_stream.hpp:94-99 (bias = starting accumulator), conv_igemm.hip conv_igemm_kernel / conv_igemm_dma_kernel LDS
 #              epilogues (acc + bias, then R)
 #   "acc2"     y = R(R(relu?(acc + bias)) + old)          two roundings: the tile is rounded into the LDS staging tile first, the
-#              destination added to the ROUNDED value (conv3x3_halo.hpp:335, _pp.hpp:385, _pp128.hpp:430, _ws.hpp:358,
+#              destination added to the ROUNDED value (conv3x3_halo.hpp:316, _pp.hpp:376, _pp128.hpp:395, _ws.hpp:354,
 #              conv1x1_stream.hpp:125, conv_gemm256.hpp:231, conv_igemm.hip (both 2-byte epilogues))
 #   "pool2"    y = R(sum_2x2 R(acc))                     the four outputs of a 2x2 group are rounded, summed in fp32, rounded again
-#              (conv3x3_halo.hpp:303-313, _pp.hpp:361-371, _pp128.hpp:382-392, _ws.hpp:330-340)
-#   "pool2acc" y = R(sum_2x2 R(acc) + old)               ... with the destination added before the second rounding (:310 / :368 /
-#              :389 / :337)
+#              (conv3x3_halo.hpp:284-294, _pp.hpp:352-362, _pp128.hpp:371-381, _ws.hpp:326-336)
+#   "pool2acc" y = R(sum_2x2 R(acc) + old)               ... with the destination added before the second rounding (:291 / :359 /
+#              :378 / :333)
 #   "fp32"     y = relu?(acc + bias) (+ old), all fp32    conv_igemm_kernel<float> (conv_igemm.hip, !LDS_EPI branch); the weight
 #              gradients (fp32 partial slabs, fp32 split reduction with beta)
 # variant (mi355_conv2d_igemm_variant_n) -> the models of the epilogues it serves (accumulate bit 0, ReLU bit 1, 2x2 sum bit 2)
