@@ -443,6 +443,21 @@ int mi355_overlay_heatmap(const uint8_t* img, int B, int H, int W, const float* 
 int mi355_seg_counts(const float* prob_or_logit, const float* target, float* counts, int B, long long per,
                      int is_logit, float thr, mi355_stream_t s);
 
+/* ---- surface-distance metrics (Hausdorff, HD95, ASSD, surface Dice; nothing in the reference, whose tester.py stops at the
+ * overlap metrics above) ----------------------------------------------------------------------------------------------- */
+/* Per sample b of [B][H][W] fp32 maps, binarised exactly as mi355_seg_counts does (P = prob > thr, T = target > thr): the border
+ * of a mask is its pixels with a 4-neighbour outside it (outside the image counts as background), d2_PT(p) = min over the
+ * border of T of |p - q|^2 for p on the border of P, d2_TP likewise: integers for unit pixel spacing.
+ *   out_i[b][0..8) = n_P, n_T, max d2_PT, max d2_TP, lo2, hi2, #{d2_PT <= tol2}, #{d2_TP <= tol2}
+ *   out_d[b][0..2) = sum sqrt(d2_PT), sum sqrt(d2_TP)       (fp64, added in a fixed order)
+ * lo2 = d2[lo], hi2 = d2[lo + (r > 0)] of the ascending concatenation of both sets, lo = q (n - 1) div 100, r = q (n - 1) mod 100,
+ * n = n_P + n_T (numpy.percentile's two neighbours).  n = 0: everything 0.  Exactly one border empty: the two counts, the rest 0.
+ * 1 <= H, W <= 1024.  `ws` = mi355_surface_ws_ints(B, H, W) int32 elements of scratch (-1 + last_error when the shape is
+ * unsupported); no floating-point atomics: the same input gives the same bytes. */
+int mi355_surface_ws_ints(int B, int H, int W);
+int mi355_surface_distances(const float* pred, const float* target, int B, int H, int W, int is_logit, float thr, int q,
+                            int tol2, int32_t* ws, long long ws_ints, int32_t* out_i, double* out_d, mi355_stream_t s);
+
 /* ---- launch-plan replay: the per-batch host loop of utils/helpers.py:317-342 (model(x) ... loss.backward()) as ONE call ---- */
 /* A plan is a table of pre-resolved launches of the entry points above: `name`, its arguments as 64-bit slots in prototype
  * order INCLUDING the trailing stream (pointers and integers by value, floats as their IEEE-754 bit pattern in the low 32

@@ -1,7 +1,10 @@
 """Evaluation metrics and loops of the MI355X path — same names and return values as the
 reference's utils/tester.py (segmentation metrics :92-193, classification metrics :49-88, eval
 loops :197-312).  Per-sample counters come from one HIP reduction per batch instead of ~9 host
-syncs per sample."""
+syncs per sample.  On request (``surface=True`` / ``--surface``) the segmentation loop also reports
+the boundary metrics the reference lacks: Hausdorff distance, HD95, ASSD and surface Dice
+(csrc/surface.hip; DESIGN.md, "Surface-distance metrics")."""
+import math
 import os
 
 import sys
@@ -70,6 +73,88 @@ def calculate_segmentation_metrics(pred, target, threshold=0.5):
     return _single(pred, target, threshold)
 
 
+# ---- surface-distance metrics (nothing in the reference; definition in DESIGN.md and tests/surface_ref.py) ----------------
+SURFACE_KEYS = ("hausdorff", "hd95", "assd", "surface_dice")
+
+
+def _surface_values(out_i, out_d, spacing, q, xp):
+    """The four per-sample metrics from mi355_surface_distances' raw output, in float64, on numpy arrays (xp = np) or torch
+    tensors (xp = torch: device arithmetic, nothing is read back).  out_i [B, 8] = n_P, n_T, max d2_PT, max d2_TP, d2[lo], d2[hi],
+    #{d2_PT <= tol2}, #{d2_TP <= tol2}; out_d [B, 2] = sum d_PT, sum d_TP.  Both borders empty: 0, 0, 0, 1; one empty: NaN."""
+    f = (lambda a: a.astype(np.float64)) if xp is np else (lambda a: a.double())
+    n_p, n_t, m_pt, m_tp, lo2, hi2, w_pt, w_tp = (f(out_i[:, k]) for k in range(8))
+    s_pt, s_tp = f(out_d[:, 0]), f(out_d[:, 1])
+    n = n_p + n_t
+    one = lambda a: xp.clip(a, 1.0, None)
+    r = xp.remainder(q * xp.clip(n - 1.0, 0.0, None), 100.0) / 100.0       # integers below 2^53: exact
+    res = {"hausdorff": spacing * xp.sqrt(xp.maximum(m_pt, m_tp)),
+           "hd95": spacing * ((1.0 - r) * xp.sqrt(lo2) + r * xp.sqrt(hi2)),
+           "assd": spacing * 0.5 * (s_pt / one(n_p) + s_tp / one(n_t)),
+           "surface_dice": (w_pt + w_tp) / one(n) + f(n == 0)}
+    undefined = (n_p == 0) != (n_t == 0)
+    nan = xp.full_like(n, float("nan"))
+    return {k: xp.where(undefined, nan, v) for k, v in res.items()}
+
+
+def _surface_from_raw(out_i, out_d, spacing=1.0, q=95):
+    """numpy: raw arrays of mi355_surface_distances -> {"hausdorff", "hd95", "assd", "surface_dice"}, float64 arrays [B]."""
+    return _surface_values(np.asarray(out_i).reshape(-1, 8), np.asarray(out_d).reshape(-1, 2), float(spacing), int(q), np)
+
+
+def _surface_tol2(tolerance, spacing):
+    """d * spacing <= tolerance as an integer bound on d^2 (the relative 1e-12 keeps ratios like 0.3 / 0.1 on the integer meant)"""
+    if not (spacing > 0 and tolerance >= 0):
+        raise ValueError(f"surface metrics: spacing must be positive and tolerance non-negative ({spacing}, {tolerance})")
+    return int(min(math.floor((tolerance / spacing) ** 2 * (1.0 + 1e-12)), 2 ** 31 - 1))
+
+
+def _surface_raw(pred, target, is_logit, threshold, percentile, tol2):
+    """Launch mi355_surface_distances on [B,1,H,W] / [B,H,W] maps -> (out_i int32 [B, 8], out_d float64 [B, 2]) on the device."""
+    if pred.dim() == 4:
+        if pred.shape[1] != 1:
+            raise ValueError(f"surface metrics are defined for one-channel masks, got C={pred.shape[1]}")
+        pred = pred[:, 0]
+    if target.dim() == 4:
+        if target.shape[1] != 1:
+            raise ValueError(f"surface metrics are defined for one-channel masks, got C={target.shape[1]} (target)")
+        target = target[:, 0]
+    if pred.dim() != 3 or pred.shape != target.shape:
+        raise ValueError(f"surface metrics: [B,1,H,W] or [B,H,W] maps of one shape expected, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if int(percentile) != percentile or not 0 <= percentile <= 100:
+        raise ValueError(f"surface metrics: percentile must be an integer in 0..100, got {percentile}")
+    if not pred.is_cuda:
+        pred = pred.cuda()
+    target = target.to(pred.device)
+    B, H, W = pred.shape
+    n = lib.raw("mi355_surface_ws_ints")(B, H, W)
+    if n < 0:
+        raise RuntimeError(f"mi355_surface_ws_ints failed: {lib.raw('mi355_last_error')().decode()}")
+    ws = torch.empty(n, dtype=torch.int32, device=pred.device)
+    out_i = torch.empty(B, 8, dtype=torch.int32, device=pred.device)
+    out_d = torch.empty(B, 2, dtype=torch.float64, device=pred.device)
+    lib.mi355_surface_distances(pred.float().contiguous(), target.float().contiguous(), B, H, W, 1 if is_logit else 0, float(threshold),
+                                int(percentile), tol2, ws, n, out_i, out_d)
+    return out_i, out_d
+
+
+def surface_metrics_batch(pred, target, is_logit=False, threshold=0.5, spacing=1.0, percentile=95, tolerance=2.0):
+    """Per-sample Hausdorff distance, its percentile (HD95 by default), average symmetric surface distance (in units of
+    ``spacing``) and surface Dice at ``tolerance`` (same unit) of [B,1,H,W] / [B,H,W] maps, H, W <= 1024: float64 device tensors
+    [B] (NaN where exactly one of the two masks has no border), plus the raw output under "out_i" / "out_d".  Four launches and
+    a few element-wise ops on the current stream; nothing synchronises with the host — reading the values back is the caller's."""
+    out_i, out_d = _surface_raw(pred, target, is_logit, threshold, percentile, _surface_tol2(tolerance, spacing))
+    res = _surface_values(out_i, out_d, float(spacing), int(percentile), torch)
+    res["out_i"], res["out_d"] = out_i, out_d
+    return res
+
+
+def calculate_surface_metrics(pred, target, threshold=0.5, spacing=1.0, percentile=95, tolerance=2.0):
+    """One sample ([H,W] or [1,H,W] probabilities, like calculate_segmentation_metrics) -> dict of four floats."""
+    H, W = pred.shape[-2:]
+    res = surface_metrics_batch(pred.reshape(1, H, W), target.reshape(1, H, W), False, threshold, spacing, percentile, tolerance)
+    return {k: float(res[k][0]) for k in SURFACE_KEYS}
+
+
 def calculate_classification_metrics(all_preds, all_labels):
     """Accuracy and support-weighted precision/recall/F1 (+ per class, confusion matrix), the
     quantities sklearn's *_score(average="weighted", zero_division=0) return (tester.py:49-88)."""
@@ -117,7 +202,9 @@ def test_classification_model(model, test_loader, device, model_name):
     return m
 
 
-def test_segmentation_model(model, test_loader, device, model_name):
+def test_segmentation_model(model, test_loader, device, model_name, surface=False):
+    """``surface=True`` adds hausdorff, hd95, assd (pixels; mean over the samples where both masks have a border), surface_dice
+    (%, tolerance 2 pixels) and surface_samples (how many samples entered those means) behind the six overlap metrics."""
     model.eval()
     tot = {k: 0.0 for k in ("iou", "dice", "pixel_accuracy", "precision", "recall", "f1")}
     n = 0
@@ -132,17 +219,29 @@ def test_segmentation_model(model, test_loader, device, model_name):
             B, per = out.shape[0], out[0].numel()
             cnt = torch.empty(B, 4, dtype=torch.float32, device=out.device)
             lib.mi355_seg_counts(out.float().contiguous(), masks.float().contiguous(), cnt, B, per, 1, 0.5)
-            pending.append((cnt, per))
-    for cnt, per in pending:                      # single read-back after the loop
+            pending.append((cnt, per, _surface_raw(out, masks, True, 0.5, 95, 4) if surface else None))
+    surf = []
+    for cnt, per, raw in pending:                 # single read-back after the loop
         for c in cnt.double().cpu().numpy():
             m = _metrics_from_counts(c, per)
             for k in tot:
                 tot[k] += m[k]
             n += 1
+        if raw is not None:
+            surf.append(_surface_from_raw(raw[0].cpu().numpy(), raw[1].cpu().numpy(), 1.0, 95))
     avg = {k: v / n for k, v in tot.items()}
+    if surface:
+        per_sample = {k: np.concatenate([s[k] for s in surf]) for k in SURFACE_KEYS}
+        ok = ~np.isnan(per_sample["hausdorff"])
+        for k in SURFACE_KEYS:
+            avg[k] = float(per_sample[k][ok].mean()) * (100.0 if k == "surface_dice" else 1.0) if ok.any() else float("nan")
+        avg["surface_samples"] = int(ok.sum())
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
     print(f"IoU (Jaccard):     {avg['iou']:.2f}%\nDice Coefficient:  {avg['dice']:.2f}%\nPixel Accuracy:    {avg['pixel_accuracy']:.2f}%")
-    print(f"Precision:         {avg['precision']:.2f}%\nRecall:            {avg['recall']:.2f}%\nF1 Score:          {avg['f1']:.2f}%\n{'=' * 60}\n")
+    print(f"Precision:         {avg['precision']:.2f}%\nRecall:            {avg['recall']:.2f}%\nF1 Score:          {avg['f1']:.2f}%"
+          + (f"\nHausdorff:         {avg['hausdorff']:.2f} px\nHD95:              {avg['hd95']:.2f} px\nASSD:              {avg['assd']:.2f} px\n"
+             f"Surface Dice @2px: {avg['surface_dice']:.2f}% ({avg['surface_samples']} of {n} samples)" if surface else "")
+          + f"\n{'=' * 60}\n")
     return avg
 
 
@@ -154,14 +253,15 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None):
+                    seg_weights_dir=None, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
     decode, transforms on the GPU), batch_size for classification and batch_size // 2 for segmentation (:663); a caller may pass
     its own loaders instead, and when neither exists the reference's "dataset not found" branch is taken (:637-639, :729-731).
     The CLIP / CLIPSeg entries (hub models, out of scope: SURVEY.md section 8) are reported and skipped.  Checkpoints are the
-    reference's own format: a plain `state_dict` saved by `train` (helpers.py:394-400)."""
+    reference's own format: a plain `state_dict` saved by `train` (helpers.py:394-400).  ``surface=True`` adds the surface-distance
+    metrics to every segmentation result (test_segmentation_model)."""
     from utils.helpers import get_class_model, get_seg_model
     if not torch.cuda.is_available():
         raise RuntimeError("test_all_models: the MI355X path needs a GPU (the reference falls back to the CPU, tester.py:524)")
@@ -223,7 +323,8 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     elif len(seg_loader.dataset) == 0:
         print("\n[WARNING] Segmentation test dataset is empty. Skipping segmentation testing.")
     else:
-        run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, test_segmentation_model, "Segmentation")
+        seg_test = (lambda m, l, d, name: test_segmentation_model(m, l, d, name, surface=True)) if surface else test_segmentation_model
+        run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
     return results
 
 
@@ -257,6 +358,16 @@ def print_summary(results):
             print(f"{model:<20} {m['iou']:>8.2f}% {m['dice']:>8.2f}% {m['precision']:>10.2f}% {m['recall']:>10.2f}% {m['f1']:>10.2f}%")
         best = max(seg_models, key=lambda x: results[x]["dice"])
         print(f"\n\U0001F3C6 Best Segmentation Model: {best} (Dice: {results[best]['dice']:.2f}%)")
+        surf_models = [m for m in seg_models if all(k in results[m] for k in SURFACE_KEYS)]
+        if surf_models:                                     # (only after test_all_models(surface=True))
+            print("\n\nSEGMENTATION MODELS, SURFACE DISTANCES (pixels; surface Dice at 2 px):")
+            print("-" * 80)
+            print(f"{'Model':<20} {'Hausdorff':<12} {'HD95':<12} {'ASSD':<12} {'Surface Dice':<14} {'Samples':<8}")
+            print("-" * 80)
+            for model in surf_models:
+                m = results[model]
+                print(f"{model:<20} {m['hausdorff']:>10.2f}   {m['hd95']:>10.2f}   {m['assd']:>10.2f}   {m['surface_dice']:>11.2f}%   "
+                      f"{m.get('surface_samples', ''):>7}")
     print("=" * 80 + "\n")
 
 
@@ -295,10 +406,14 @@ def save_results_to_csv(results, cls_output_path="results/classification_test_re
 
 
 if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898): same banner, same three calls
+    import argparse
+    _ap = argparse.ArgumentParser(description="Test every checkpoint under weights/ on the test split")
+    _ap.add_argument("--surface", action="store_true", help="also report Hausdorff, HD95, ASSD and surface Dice of the segmentation models")
+    _args = _ap.parse_args()
     print("\n" + "=" * 80)
     print(" " * 20 + "MODEL TESTING UTILITY")
     print("=" * 80)
-    results = test_all_models(device="cuda", batch_size=16)
+    results = test_all_models(device="cuda", batch_size=16, surface=True) if _args.surface else test_all_models(device="cuda", batch_size=16)
     print_summary(results)
     save_results_to_csv(results, cls_output_path="classification_test_results.csv", seg_output_path="segmentation_test_results.csv")
     print("\n[INFO] Testing complete!")
