@@ -118,6 +118,14 @@ int mi355_conv2d_igemm_dma_tile(int N, int Ho, int Wo, int Ci, int Co);
 int mi355_conv2d_igemm_generic_tile(int N, int Ho, int Wo, int Co);      /* ... and of the generic kernel (variant 0; fp32) */
 int mi355_conv2d_igemm_stat_rows(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW,
                                  int mul, int kmul, int off, int div, int up, int dtype);
+/* Whether the kernel the launcher runs for this batch has the 2x2-sum epilogue (bit 2 of `accumulate`): the halo kernels only, so
+ * 0 wherever mi355_conv2d_igemm_variant_n is not one of them, fp32 included. */
+int mi355_conv2d_igemm_pool2_ok(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW,
+                                int mul, int kmul, int off, int div, int up, int dtype);
+/* Name of the kernel instantiation the launcher runs for this batch, as bench.py's per-kernel table books it (NULL: unknown dtype).
+ * The string lives in a thread-local buffer: valid until the calling thread's next call. */
+const char* mi355_conv2d_igemm_kernel_name(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW,
+                                           int mul, int kmul, int off, int div, int up, int dtype);
 
 /* Weight gradient: ws[split][Co][KH*KW][Ci] = sum over the split's pixel range of
  * dy[m][co] * x[src(m,kh,kw)][ci] (forward addressing as above), then
@@ -129,6 +137,9 @@ int mi355_conv2d_wgrad_splits(int N, int Ho, int Wo, int Ci, int Co, int KH, int
  * (3x3 / stride 1 / pad 1, Ho % 8 == 0): 1 = four waves, rows of 32-pixel segments; 2 = four waves, 16-pixel-wide images two at a
  * time; 3 = eight waves, rows of 64-pixel segments (wgrad3x3_halo8_kernel); 4 = eight waves, 32-pixel-wide images two at a time. */
 int mi355_conv2d_wgrad_variant(int N, int Ho, int Wo, int KH, int KW, int stride, int pad, int dtype);
+/* Name of the kernel of that answer, as bench.py's per-kernel table books it (shape-level, like the variant query).  The string is
+ * static or lives in a thread-local buffer: valid until the calling thread's next call. */
+const char* mi355_conv2d_wgrad_kernel_name(int N, int Ho, int Wo, int Ci, int Co, int KH, int KW, int stride, int pad, int dtype);
 int mi355_conv2d_wgrad(const void* x, const void* dy, float* ws, int splits,
                        int N, int Hi, int Wi, int Ci, int ldx,
                        int Ho, int Wo, int Co, int ldy,

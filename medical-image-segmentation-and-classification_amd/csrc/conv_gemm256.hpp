@@ -235,12 +235,13 @@ __global__ __launch_bounds__(512, 2) void conv_gemm256_kernel(const ConvArgs a, 
 }
 
 // 0: not served; 1: mode 0 (1x1 / 2x2 stride-2 gather), 2: mode 1 (ConvTranspose2d(2, 2) forward phases)
-static int gemm256_mode(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul, int off, int div, int up) {
-  if (up || off != 0 || KH != KW || Ci % 64 != 0 || Co % 128 != 0) return 0;
-  if (KH == 1 && div == 1 && (mul == 1 || mul == 2) && (long long)(Ho - 1) * mul < Hi && (long long)(Wo - 1) * mul < Wi)
-    return ((long long)N * Ho * Wo) % 256 == 0 ? 1 : 0;
-  if (KH == 2 && div == 1 && mul == 2 && kmul == 1 && 2 * Ho == Hi && 2 * Wo == Wi) return ((long long)N * Ho * Wo) % 256 == 0 ? 1 : 0;
-  if (KH == 2 && div == 2 && mul == 1 && kmul == -1 && Ho == 2 * Hi && Wo == 2 * Wi) return ((long long)N * Hi * Wi) % 256 == 0 ? 2 : 0;
+static int gemm256_mode(const ConvShape& s) {
+  if (s.up || s.off != 0 || s.KH != s.KW || s.Ci % 64 != 0 || s.Co % 128 != 0) return 0;
+  const long long out_px = (long long)s.N * s.Ho * s.Wo, in_px = (long long)s.N * s.Hi * s.Wi;
+  if (s.KH == 1 && s.div == 1 && (s.mul == 1 || s.mul == 2) && (long long)(s.Ho - 1) * s.mul < s.Hi && (long long)(s.Wo - 1) * s.mul < s.Wi)
+    return out_px % 256 == 0 ? 1 : 0;
+  if (s.KH == 2 && s.div == 1 && s.mul == 2 && s.kmul == 1 && 2 * s.Ho == s.Hi && 2 * s.Wo == s.Wi) return out_px % 256 == 0 ? 1 : 0;
+  if (s.KH == 2 && s.div == 2 && s.mul == 1 && s.kmul == -1 && s.Ho == 2 * s.Hi && s.Wo == 2 * s.Wi) return in_px % 256 == 0 ? 2 : 0;
   return 0;
 }
 static long long gemm256_tiles(int mode, int N, int Hi, int Wi, int Ho, int Wo, int Co) {

@@ -496,13 +496,19 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
   }
 }
 
-template <typename T, int BN, int BK, int NS>
-static int launch_dma(const ConvArgs& a, hipStream_t s) {
-  const int grid = ceil_div(a.M, 128) * (a.Co / BN);
-  hipLaunchKernelGGL((conv_igemm_dma_kernel<T, BN, BK, NS>), dim3(grid), dim3(256), 0, s, a);
+// a generic / LDS-DMA ring kernel instantiation on its grid of 128 x BN output tiles
+template <auto KERNEL, int BN>
+static int launch_tiles(const ConvArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(KERNEL, dim3(ceil_div(a.M, 128) * (a.Co / BN)), dim3(256), 0, s, a);
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }
+template <typename T, int BN, int BK, int NS>
+static int launch_dma(const ConvArgs& a, hipStream_t s) { return launch_tiles<conv_igemm_dma_kernel<T, BN, BK, NS>, BN>(a, s); }
+
+// One convolution as the host side sees it: built once at each extern "C" boundary, read by everything that decides or describes
+// the launch.  (Field order = argument order of the queries.)
+struct ConvShape { int N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype; };
 
 #include "conv3x3_halo.hpp"
 #include "conv3x3_halo_pp.hpp"
@@ -511,75 +517,30 @@ static int launch_dma(const ConvArgs& a, hipStream_t s) {
 #include "conv1x1_stream.hpp"
 #include "conv_gemm256.hpp"
 
-template <typename T, int BN, int BK>
-static int launch(const ConvArgs& a, hipStream_t s) {
-  const int grid = ceil_div(a.M, 128) * (a.Co / BN);
-  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, BK>), dim3(grid), dim3(256), 0, s, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
-}
-
-// (generic kernel: the widest output-channel tile that divides Co, narrower when that grid would be at most half a round of
-//  workgroups — ResNet-18 at batch 8, fp32: 512 -> 512 @8² is 4 x 4 tiles of 128 x 128; see dma_tile_n)
-static int small_grid_tile_n(long long M, int Co);
 template <typename T, int BK>
-static int launch_bn(const ConvArgs& a, hipStream_t s) {
-  switch (small_grid_tile_n(a.M, a.Co)) {
-    case 128: return launch<T, 128, BK>(a, s);
-    case 64: return launch<T, 64, BK>(a, s);
-    default: return launch<T, 32, BK>(a, s);
+static int launch_bn(const ConvArgs& a, hipStream_t s, int bn) {
+  switch (bn) {
+    case 128: return launch_tiles<conv_igemm_kernel<T, 128, BK>, 128>(a, s);
+    case 64: return launch_tiles<conv_igemm_kernel<T, 64, BK>, 64>(a, s);
+    default: return launch_tiles<conv_igemm_kernel<T, 32, BK>, 32>(a, s);
   }
 }
 
 enum IgemmVariant { IG_GENERIC = 0, IG_DMA, IG_HALO_8x32, IG_HALO_16x16, IG_STREAM1x1, IG_HALO_PP, IG_HALO_PP128, IG_WS64, IG_WS128, IG_GEMM256 };
 
-// ONE place that decides which kernel serves a shape (also used by the statistics-row query).
-static IgemmVariant pick_variant(int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul, int off,
-                                 int div, int up, int dtype) {
-  if (!dtype_is_2byte(dtype)) return IG_GENERIC;
-  static const int force_generic = getenv("MI355_IGEMM_VARIANT") ? atoi(getenv("MI355_IGEMM_VARIANT")) == 0 : 0;
-  if (force_generic) return IG_GENERIC;
-  const int Hlog = up ? 2 * Hi : Hi, Wlog = up ? 2 * Wi : Wi;
-  // 3x3 stride-1 pad-1 forward / data gradient on tile-divisible images: halo-patch kernel
-  const bool is3x3s1 = KH == 3 && KW == 3 && mul == 1 && div == 1 && Ho == Hlog && Wo == Wlog &&
-                       ((kmul == 1 && off == -1) || (kmul == -1 && off == 1 && !up));
-  if (is3x3s1 && Co % 64 == 0) {
-    // MI355_HALO_PP=1: 16 x 32 tiles, two phase-shifted halves per 512-thread workgroup (conv3x3_halo_pp.hpp).  Measured
-    // (profiles/r02a_*): +1-3 % on the 32x32 layers with Ci >= 512, -10-15 % on the 256x256 layers (one workgroup per CU
-    // exposes every tile's prologue and epilogue) -> the 4-wave kernel below stays the default; the variant is kept selectable.
-    static const int use_pp = getenv("MI355_HALO_PP") ? atoi(getenv("MI355_HALO_PP")) : 0;
-    if (use_pp && Wo % 32 == 0 && Ho % 16 == 0) return IG_HALO_PP;
-    // 16 x 32 pixels x 128 channels, ping-pong halves (conv3x3_halo_pp128.hpp): half the operand bytes per FLOP; one workgroup
-    // per CU, so only where the reduction is deep enough to amortise a tile's prologue and epilogue.  Measured per layer
-    // (profiles/r02c_conv_layers.txt against r02a_conv_layers_pp0.txt): Ci >= 512 +14-17 %, Ci = 256 +7-9 %, Ci = 128 -2..+2 % -> threshold 256.
-    // MI355_HALO_PP128=0 switches it off (A/B), MI355_HALO_PP128_MINCI moves the threshold.
-    static const int pp128 = getenv("MI355_HALO_PP128") ? atoi(getenv("MI355_HALO_PP128")) : 1;
-    static const int pp128_min_ci = getenv("MI355_HALO_PP128_MINCI") ? atoi(getenv("MI355_HALO_PP128_MINCI")) : 256;
-    if (pp128 && Co % 128 == 0 && Ci % 64 == 0 && Ci >= pp128_min_ci && Wo % 32 == 0 && Ho % 16 == 0) return IG_HALO_PP128;
-    // Ci = 64 / 128: weights stationary in registers, persistent workgroups (conv3x3_ws.hpp); MI355_WS64=0 / MI355_WS128=0 switch
-    // them off (A/B)
-    static const int ws64 = getenv("MI355_WS64") ? atoi(getenv("MI355_WS64")) : 1;
-    static const int ws128 = getenv("MI355_WS128") ? atoi(getenv("MI355_WS128")) : 1;
-    const int ws_rows = ws_tile_rows(Ci, Ho, Wo, Co);
-    if (ws64 && ws_rows == 8) return IG_WS64;
-    if (ws128 && ws_rows == 4) return IG_WS128;
-    if (Wo % 32 == 0 && Ho % 8 == 0) return IG_HALO_8x32;
-    if (Wo % 16 == 0 && Ho % 16 == 0) return IG_HALO_16x16;
-  }
-  // narrow pointwise convolutions (and their data gradients): register-resident weights, streaming pixels
-  if (KH == 1 && KW == 1 && mul == 1 && div == 1 && !up && off == 0 && Ho == Hi && Wo == Wi && stream1x1_shape(Ci, Co))
-    return IG_STREAM1x1;
-  // padding-free convolutions as plain GEMMs on 256 x 128 tiles (conv_gemm256.hpp): 1x1, 2x2 / stride 2, ConvTranspose2d(2, 2) phases;
-  // batch-dependent conditions (row count, grid size) in final_variant.  MI355_GEMM256=0 switches it off (A/B)
-  static const int use_gemm256 = getenv("MI355_GEMM256") ? atoi(getenv("MI355_GEMM256")) : 1;
-  if (use_gemm256 && gemm256_mode(256, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up)) return IG_GEMM256;
-  if (Co % 64 != 0 && Ci % 64 != 0) return IG_GENERIC;      // 32-wide tile with a 32-deep slab: too few DMA pieces per wave
-  return IG_DMA;
-}
+// ---- Host side: which kernel serves a convolution.  choose() is the ONE place that decides; the launcher, the queries and the
+// kernel names all read the ConvChoice it returns. ----
+struct ConvChoice {
+  IgemmVariant variant;         // what the launcher runs for this batch (mi355_conv2d_igemm_variant_n)
+  IgemmVariant shape_variant;   // the shape-level answer, N left out (mi355_conv2d_igemm_variant)
+  int bn, bk, ns;               // generic and LDS-DMA ring kernels: the <BN, BK, NS> instantiated (NS = 0: generic)
+  int gemm256;                  // IG_GEMM256: the mode of conv_gemm256.hpp
+  int stat_rows;                // statistics partial rows the kernel leaves (0 = no statistics epilogue: run mi355_bn_stats)
+  bool pool2;                   // the 2x2-sum epilogue exists
+};
 
-// The 128-channel ping-pong kernel runs ONE 512-thread workgroup per CU: a grid that leaves a quarter of the last round of
-// workgroups empty (or does not fill the chip once: 32 images of 32 x 32 x 256 channels = 128 workgroups) is served by the
-// 4-wave kernel, whose grid is four times finer.  Batch-dependent, hence not part of the shape-level variant query.
+// Every MI355_* switch of the decision (A/B switches unless said otherwise), read once per process.
+static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
 static int device_cus() {
   static const int cus = [] {
     int dev = 0, n = 0;
@@ -588,108 +549,203 @@ static int device_cus() {
   }();
   return cus;
 }
-static IgemmVariant resolve_variant(IgemmVariant v, int N, int Ho, int Wo, int Co) {
-  // the weight-stationary kernel is persistent (2 workgroups per CU): it wants at least two tiles per workgroup to amortise
-  // its weight load, else the 4-wave kernel with its four-times finer grid
-  // (MI355_WS64_MIN_TILES lowers the threshold: the parity tests run it on small shapes, one tile per workgroup included)
-  if (v == IG_WS64 || v == IG_WS128) {
-    static const long long min_tiles = getenv("MI355_WS64_MIN_TILES") ? atoll(getenv("MI355_WS64_MIN_TILES")) : 4ll * device_cus();
-    const int th = v == IG_WS64 ? 8 : 4;
-    const long long S = (long long)N * (Ho / th) * (Wo / 32);
-    // (the 128-channel instantiation loads twice the weights per workgroup for tiles half as tall: measured per layer it wins
-    //  from 16 tiles per workgroup up — 128² x 128 -> 128 / 256, 256² x 128 -> 64: +3 ... +10 % — and loses 1-6 % at 8 —
-    //  64² x 128 -> 256, 128² x 128 -> 64, batch-16 layers — so its threshold is 12 tiles per workgroup = 24 x CUs)
-    static const int mult128 = getenv("MI355_WS128_TILE_MULT") ? atoi(getenv("MI355_WS128_TILE_MULT")) : 6;      // (A/B switch)
-    if (S >= 8 && S * (Co / 64) >= min_tiles * (v == IG_WS128 ? mult128 : 1)) return v;
-    return Ho % 8 == 0 ? IG_HALO_8x32 : (Ho % 16 == 0 && Wo % 16 == 0 ? IG_HALO_16x16 : IG_DMA);
-  }
-  if (v != IG_HALO_PP128) return v;
-  const int cus = device_cus();
-  const long long grid = (long long)N * (Ho / 16) * (Wo / 32) * (Co / 128);
-  const long long rounds = (grid + cus - 1) / cus;
-  static const int fill = getenv("MI355_PP128_FILL") ? atoi(getenv("MI355_PP128_FILL")) : 80;      // (A/B switch, percent)
-  return grid * 100 >= rounds * cus * fill ? IG_HALO_PP128 : IG_HALO_8x32;     // >= 80 % of the last round filled
-}
-
-// Output-channel tile of the LDS-DMA ring kernel: the widest that divides Co — unless its grid leaves most of the chip idle (the
-// frozen ResNet-50 encoder's 8 x 8 and 16 x 16 layers at batch 32: M = 2048 rows x 512 channels = 64 workgroups of 128 x 128), then
-// the next narrower one (twice / four times the workgroups).  MI355_DMA_SMALLGRID=0: always the widest (A/B).
-static int small_grid_tile_n(long long M, int Co) {
-  static const int small = getenv("MI355_DMA_SMALLGRID") ? atoi(getenv("MI355_DMA_SMALLGRID")) : 1;
-  const long long rows = (M + 127) / 128;
-  int bn = Co % 128 == 0 ? 128 : (Co % 64 == 0 ? 64 : 32);
-  if (small) {
-    const int cus = device_cus();
-    if (bn == 128 && rows * (Co / 128) * 2 <= cus) bn = 64;
-    if (bn == 64 && rows * (Co / 64) * 2 <= cus) bn = 32;
-  }
-  return bn;
-}
-
-static int dma_tile_n(long long M, int Ci, int Co) {
-  static const int small = getenv("MI355_DMA_SMALLGRID") ? atoi(getenv("MI355_DMA_SMALLGRID")) : 1;
-  const long long rows = (M + 127) / 128;
-  int bn = Co % 128 == 0 ? 128 : (Co % 64 == 0 ? 64 : 32);
-  if (small) {
-    const int cus = device_cus();
-    if (bn == 128 && rows * (Co / 128) * 2 <= cus) bn = 64;                       // at most half a round of workgroups
-    if (bn == 64 && Ci % 64 == 0 && rows * (Co / 64) * 2 <= cus) bn = 32;         // (the 32-wide instance runs 64-channel K tiles)
-  }
-  return bn;
-}
+struct Switches {
+  int force_generic = getenv("MI355_IGEMM_VARIANT") ? atoi(getenv("MI355_IGEMM_VARIANT")) == 0 : 0;
+  int halo_pp = env_int("MI355_HALO_PP", 0);
+  int pp128 = env_int("MI355_HALO_PP128", 1), pp128_min_ci = env_int("MI355_HALO_PP128_MINCI", 256);   // =0: off; the Ci threshold
+  int pp128_fill = env_int("MI355_PP128_FILL", 80);                                                      // percent of the last round
+  int ws64 = env_int("MI355_WS64", 1), ws128 = env_int("MI355_WS128", 1);                                // =0: off
+  // (lowers the threshold: the parity tests run the weight-stationary kernels on small shapes, one tile per workgroup included)
+  long long ws_min_tiles = getenv("MI355_WS64_MIN_TILES") ? atoll(getenv("MI355_WS64_MIN_TILES")) : 4ll * device_cus();
+  int ws128_tile_mult = env_int("MI355_WS128_TILE_MULT", 6);
+  int gemm256 = env_int("MI355_GEMM256", 1);                                                             // =0: off
+  long long gemm256_min_tiles = getenv("MI355_GEMM256_MIN_TILES") ? atoll(getenv("MI355_GEMM256_MIN_TILES")) : 128;
+  int dma_smallgrid = env_int("MI355_DMA_SMALLGRID", 1);                                                 // =0: always the widest tile
+};
+static const Switches& switches() { static const Switches sw{}; return sw; }
 
 static bool halo_family(IgemmVariant v) {
   return v == IG_HALO_8x32 || v == IG_HALO_16x16 || v == IG_HALO_PP || v == IG_HALO_PP128 || v == IG_WS64 || v == IG_WS128;
 }
 static bool image_fits_descriptor(int Hi, int Wi, int ldi, int esz) { return (long long)Hi * Wi * ldi * esz < (1ll << 31); }
-static IgemmVariant final_variant(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul, int off,
-                                  int div, int up, int dtype) {
-  IgemmVariant v = resolve_variant(pick_variant(Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype), N, Ho, Wo, Co);
-  if (v == IG_GEMM256) {      // whole 256-row tiles only, and enough of them to fill the chip once (one workgroup per CU)
-    static const long long min_tiles = getenv("MI355_GEMM256_MIN_TILES") ? atoll(getenv("MI355_GEMM256_MIN_TILES")) : 128;
-    const int gm = gemm256_mode(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up);
-    if (!gm || gemm256_tiles(gm, N, Hi, Wi, Ho, Wo, Co) < min_tiles) v = IG_DMA;
+
+// Output-channel tile of the generic and of the LDS-DMA ring kernel: the widest that divides Co — unless its grid leaves most of the
+// chip idle (at most half a round of workgroups: the frozen ResNet-50 encoder's 8 x 8 and 16 x 16 layers at batch 32: M = 2048 rows
+// x 512 channels = 64 workgroups of 128 x 128; ResNet-18 at batch 8, fp32: 512 -> 512 @8² is 4 x 4 tiles), then the next narrower
+// one (twice / four times the workgroups).  `to32`: whether the 64-wide tile may narrow to 32 (the generic kernel: always; the ring
+// kernel's 32-wide instance runs 64-channel K tiles: Ci % 64 == 0).  MI355_DMA_SMALLGRID=0: always the widest (A/B).
+static int small_grid_tile_n(long long M, int Co, bool to32) {
+  const long long rows = (M + 127) / 128;
+  int bn = Co % 128 == 0 ? 128 : (Co % 64 == 0 ? 64 : 32);
+  if (switches().dma_smallgrid) {
+    const int cus = device_cus();
+    if (bn == 128 && rows * (Co / 128) * 2 <= cus) bn = 64;
+    if (bn == 64 && to32 && rows * (Co / 64) * 2 <= cus) bn = 32;
   }
-  return halo_family(v) && !image_fits_descriptor(Hi, Wi, Ci, 2) ? IG_DMA : v;
+  return bn;
 }
 
-extern "C" int mi355_conv2d_igemm_variant(int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul, int off,
-                                          int div, int up, int dtype) {
-  return (int)pick_variant(Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype);
+// The shape-level part of the decision: what serves Hi x Wi x Ci -> Ho x Wo x Co whatever the batch.
+static IgemmVariant shape_variant(const ConvShape& s, const Switches& sw) {
+  if (!dtype_is_2byte(s.dtype) || sw.force_generic) return IG_GENERIC;
+  const int Hlog = s.up ? 2 * s.Hi : s.Hi, Wlog = s.up ? 2 * s.Wi : s.Wi;
+  // 3x3 stride-1 pad-1 forward / data gradient on tile-divisible images: halo-patch kernel
+  const bool is3x3s1 = s.KH == 3 && s.KW == 3 && s.mul == 1 && s.div == 1 && s.Ho == Hlog && s.Wo == Wlog &&
+                       ((s.kmul == 1 && s.off == -1) || (s.kmul == -1 && s.off == 1 && !s.up));
+  if (is3x3s1 && s.Co % 64 == 0) {
+    const bool t16x32 = s.Wo % 32 == 0 && s.Ho % 16 == 0;
+    // MI355_HALO_PP=1: 16 x 32 tiles, two phase-shifted halves per 512-thread workgroup (conv3x3_halo_pp.hpp).  Measured
+    // (profiles/r02a_*): +1-3 % on the 32x32 layers with Ci >= 512, -10-15 % on the 256x256 layers (one workgroup per CU
+    // exposes every tile's prologue and epilogue) -> the 4-wave kernel below stays the default; the variant is kept selectable.
+    if (sw.halo_pp && t16x32) return IG_HALO_PP;
+    // 16 x 32 pixels x 128 channels, ping-pong halves (conv3x3_halo_pp128.hpp): half the operand bytes per FLOP; one workgroup
+    // per CU, so only where the reduction is deep enough to amortise a tile's prologue and epilogue.  Measured per layer
+    // (profiles/r02c_conv_layers.txt against r02a_conv_layers_pp0.txt): Ci >= 512 +14-17 %, Ci = 256 +7-9 %, Ci = 128 -2..+2 % -> threshold 256.
+    // MI355_HALO_PP128=0 switches it off (A/B), MI355_HALO_PP128_MINCI moves the threshold.
+    if (sw.pp128 && s.Co % 128 == 0 && s.Ci % 64 == 0 && s.Ci >= sw.pp128_min_ci && t16x32) return IG_HALO_PP128;
+    // Ci = 64 / 128: weights stationary in registers, persistent workgroups (conv3x3_ws.hpp); MI355_WS64=0 / MI355_WS128=0 switch
+    // them off (A/B)
+    const int ws_rows = ws_tile_rows(s.Ci, s.Ho, s.Wo, s.Co);
+    if (sw.ws64 && ws_rows == 8) return IG_WS64;
+    if (sw.ws128 && ws_rows == 4) return IG_WS128;
+    if (s.Wo % 32 == 0 && s.Ho % 8 == 0) return IG_HALO_8x32;
+    if (s.Wo % 16 == 0 && s.Ho % 16 == 0) return IG_HALO_16x16;
+  }
+  // narrow pointwise convolutions (and their data gradients): register-resident weights, streaming pixels
+  if (s.KH == 1 && s.KW == 1 && s.mul == 1 && s.div == 1 && !s.up && s.off == 0 && s.Ho == s.Hi && s.Wo == s.Wi && stream1x1_shape(s.Ci, s.Co))
+    return IG_STREAM1x1;
+  // padding-free convolutions as plain GEMMs on 256 x 128 tiles (conv_gemm256.hpp): 1x1, 2x2 / stride 2, ConvTranspose2d(2, 2) phases
+  // (judged at a batch of whole tiles; the batch-dependent conditions follow in choose).  MI355_GEMM256=0 switches it off (A/B)
+  ConvShape whole = s; whole.N = 256;
+  if (sw.gemm256 && gemm256_mode(whole)) return IG_GEMM256;
+  if (s.Co % 64 != 0 && s.Ci % 64 != 0) return IG_GENERIC;      // 32-wide tile with a 32-deep slab: too few DMA pieces per wave
+  return IG_DMA;
 }
 
-extern "C" int mi355_conv2d_igemm_variant_n(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul,
-                                            int off, int div, int up, int dtype) {
-  return (int)final_variant(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype);
-}
-
-/* output-channel tile (128 / 64 / 32) the LDS-DMA ring kernel (variant 1) runs for N x Ho x Wo rows, Ci -> Co channels */
-extern "C" int mi355_conv2d_igemm_dma_tile(int N, int Ho, int Wo, int Ci, int Co) { return dma_tile_n((long long)N * Ho * Wo, Ci, Co); }
-extern "C" int mi355_conv2d_igemm_generic_tile(int N, int Ho, int Wo, int Co) { return small_grid_tile_n((long long)N * Ho * Wo, Co); }
-
-// Statistics partial rows the variant v leaves for this shape (0 = no statistics epilogue).  The launcher refuses a `stats`
-// buffer exactly where this is 0, so query and launcher cannot disagree.
-static int stat_rows_of(IgemmVariant v, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul,
-                        int off, int div, int up) {
+static ConvChoice choose(const ConvShape& s) {
+  const Switches& sw = switches();
+  const int cus = device_cus(), N = s.N, Ho = s.Ho, Wo = s.Wo, Co = s.Co;
+  const long long M = (long long)N * Ho * Wo;
+  ConvChoice c = {};
+  IgemmVariant v = c.shape_variant = shape_variant(s, sw);
+  // ---- batch-dependent fall-backs (hence not part of the shape-level variant query) ----
+  if (v == IG_WS64 || v == IG_WS128) {
+    // the weight-stationary kernel is persistent (2 workgroups per CU): it wants at least two tiles per workgroup to amortise
+    // its weight load, else the 4-wave kernel with its four-times finer grid
+    const long long S = (long long)N * (Ho / (v == IG_WS64 ? 8 : 4)) * (Wo / 32);
+    // (the 128-channel instantiation loads twice the weights per workgroup for tiles half as tall: measured per layer it wins
+    //  from 16 tiles per workgroup up — 128² x 128 -> 128 / 256, 256² x 128 -> 64: +3 ... +10 % — and loses 1-6 % at 8 —
+    //  64² x 128 -> 256, 128² x 128 -> 64, batch-16 layers — so its threshold is 12 tiles per workgroup = 24 x CUs)
+    if (!(S >= 8 && S * (Co / 64) >= sw.ws_min_tiles * (v == IG_WS128 ? sw.ws128_tile_mult : 1)))
+      v = Ho % 8 == 0 ? IG_HALO_8x32 : (Ho % 16 == 0 && Wo % 16 == 0 ? IG_HALO_16x16 : IG_DMA);
+  } else if (v == IG_HALO_PP128) {
+    // The 128-channel ping-pong kernel runs ONE 512-thread workgroup per CU: a grid that leaves a quarter of the last round of
+    // workgroups empty (or does not fill the chip once: 32 images of 32 x 32 x 256 channels = 128 workgroups) is served by the
+    // 4-wave kernel, whose grid is four times finer.
+    const long long grid = (long long)N * (Ho / 16) * (Wo / 32) * (Co / 128);
+    const long long rounds = (grid + cus - 1) / cus;
+    if (grid * 100 < rounds * cus * sw.pp128_fill) v = IG_HALO_8x32;     // less than 80 % of the last round filled
+  } else if (v == IG_GEMM256) {      // whole 256-row tiles only, and enough of them to fill the chip once (one workgroup per CU)
+    c.gemm256 = gemm256_mode(s);
+    if (!c.gemm256 || gemm256_tiles(c.gemm256, N, s.Hi, s.Wi, Ho, Wo, Co) < sw.gemm256_min_tiles) v = IG_DMA, c.gemm256 = 0;
+  }
+  // the halo / ping-pong / weight-stationary kernels address an image through a buffer descriptor with 32-bit lane offsets and a
+  // 2^31-byte range check (dma.hpp): an image of 2 GiB or more would be zero-filled silently — such shapes go to the LDS-DMA ring
+  // kernel with its 64-bit addresses (judged on Ci; a channel STRIDE that alone pushes an image over the limit is refused by the launcher)
+  if (halo_family(v) && !image_fits_descriptor(s.Hi, s.Wi, s.Ci, 2)) v = IG_DMA;
+  c.variant = v; c.pool2 = halo_family(v);
+  // ---- tiles of the generic and the ring kernel ----
+  const bool k64 = s.Ci % 64 == 0;
+  if (!dtype_is_2byte(s.dtype)) {
+    c.bn = small_grid_tile_n(M, Co, true), c.bk = 16;      // (32-channel K tiles measured: +2 % on 128-wide tiles, -13 % on 64-wide ones)
+  } else if (v == IG_GENERIC) {
+    c.bn = small_grid_tile_n(M, Co, true), c.bk = k64 ? 64 : 32;
+  } else if (v == IG_DMA) {
+    // measured on MI355X (AttentionUNet shapes): the 2-deep BK=64 ring (2 workgroups/CU) wins for 128-wide tiles,
+    // the 3-deep BK=32 ring (3-4 workgroups/CU) for 64-wide tiles and for Ci % 64 != 0
+    c.bn = small_grid_tile_n(M, Co, k64);
+    c.bk = c.bn == 64 || (c.bn == 128 && !k64) ? 32 : 64;
+    c.ns = c.bn == 128 && k64 ? 2 : 3;
+  }
+  // ---- statistics rows: the launcher refuses a `stats` buffer exactly where this is 0 ----
   switch (v) {
     case IG_HALO_PP:
-    case IG_HALO_PP128: return N * (Ho / 16) * (Wo / 32);
-    case IG_WS128: return ws_groups(N, Ho, Wo, Co, 4, device_cus());      // persistent kernels: one row per workgroup range
-    case IG_WS64: return ws_groups(N, Ho, Wo, Co, 8, device_cus());
-    case IG_HALO_8x32: return N * (Ho / 8) * (Wo / 32);
-    case IG_HALO_16x16: return N * (Ho / 16) * (Wo / 16);
-    case IG_DMA: return ceil_div((long long)N * Ho * Wo, 128);
-    case IG_STREAM1x1: return stream1x1_grid((long long)N * Ho * Wo);
-    case IG_GEMM256:         // one row per 256-pixel tile; the ConvTranspose2d phases have no statistics epilogue
-      return gemm256_mode(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up) == 1 ? (int)((long long)N * Ho * Wo / 256) : 0;
-    default: return 0;       // generic kernel: no fused statistics, run mi355_bn_stats
+    case IG_HALO_PP128: c.stat_rows = N * (Ho / 16) * (Wo / 32); break;
+    case IG_WS128: c.stat_rows = ws_groups(N, Ho, Wo, Co, 4, cus); break;      // persistent kernels: one row per workgroup range
+    case IG_WS64: c.stat_rows = ws_groups(N, Ho, Wo, Co, 8, cus); break;
+    case IG_HALO_8x32: c.stat_rows = N * (Ho / 8) * (Wo / 32); break;
+    case IG_HALO_16x16: c.stat_rows = N * (Ho / 16) * (Wo / 16); break;
+    case IG_DMA: c.stat_rows = ceil_div(M, 128); break;
+    case IG_STREAM1x1: c.stat_rows = stream1x1_grid(M); break;
+    case IG_GEMM256: c.stat_rows = c.gemm256 == 1 ? (int)(M / 256) : 0; break;   // one row per 256-pixel tile; the ConvTranspose2d phases have none
+    default: break;       // generic kernel: no fused statistics
   }
+  return c;
 }
 
-extern "C" int mi355_conv2d_igemm_stat_rows(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul,
-                                            int kmul, int off, int div, int up, int dtype) {
-  return stat_rows_of(final_variant(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype), N, Hi, Wi, Ci, Ho, Wo, Co,
-                      KH, KW, mul, kmul, off, div, up);
+// Geometry part of the kernel arguments; the launcher adds pointers, strides and epilogue flags.
+static ConvArgs conv_args(const ConvShape& s) {
+  ConvArgs a = {};
+  a.N = s.N; a.Hi = s.Hi; a.Wi = s.Wi; a.Ci = s.Ci;
+  a.Ho = s.Ho; a.Wo = s.Wo; a.Co = s.Co;
+  a.KH = s.KH; a.KW = s.KW; a.mul = s.mul; a.kmul = s.kmul; a.off = s.off;
+  a.dshift = s.div == 1 ? 0 : (s.div == 2 ? 1 : 2); a.up = s.up ? 1 : 0;
+  a.M = s.N * s.Ho * s.Wo; a.HoWo = s.Ho * s.Wo;
+  a.Hlog = s.up ? 2 * s.Hi : s.Hi; a.Wlog = s.up ? 2 * s.Wi : s.Wi;
+  return a;
+}
+
+// The launch-and-name switch: an instantiation gets its launch and the name bench.py's per-kernel table books it under in ONE
+// place.  With `name` (mi355_conv2d_igemm_kernel_name; never on the launch path) the name is written and nothing is launched.
+// (Names as the table has always had them: no dtype in the ring kernel's, the fp16 build under the bf16 names.)
+enum { IG_NAME_LEN = 64 };
+#define IG_KERNEL(LAUNCH, ...)            \
+  if (!name) return LAUNCH;               \
+  return snprintf(name, IG_NAME_LEN, __VA_ARGS__) < 0 ? MI355_ERR_ARG : MI355_OK
+template <typename T>
+static int launch_or_name(const ConvChoice& c, const ConvArgs& a, hipStream_t st, char* name) {
+  if constexpr (sizeof(T) == 4) {
+    IG_KERNEL((launch_bn<T, 16>(a, st, c.bn)), "conv_igemm_kernel<f32,%d,16>", c.bn);
+  } else {
+    switch (c.variant) {
+      case IG_HALO_PP: IG_KERNEL(launch_halo_pp<T>(a, st), "conv3x3_halo_pp_kernel");
+      case IG_HALO_PP128: IG_KERNEL(launch_halo_pp128<T>(a, st), "conv3x3_halo_pp128_kernel");
+      case IG_WS64: IG_KERNEL((launch_ws<T, 64, 8>(a, st, device_cus())), "conv3x3_ws_kernel<64,8>");
+      case IG_WS128: IG_KERNEL((launch_ws<T, 128, 4>(a, st, device_cus())), "conv3x3_ws_kernel<128,4>");
+      case IG_HALO_8x32: IG_KERNEL((launch_halo_rw<T, 8, 32>(a, st)), "conv3x3_halo_rw_kernel<8,32>");
+      case IG_HALO_16x16: IG_KERNEL((launch_halo_rw<T, 16, 16>(a, st)), "conv3x3_halo_rw_kernel<16,16>");
+      case IG_STREAM1x1: IG_KERNEL(launch_stream1x1<T>(a, st), "conv1x1_stream_kernel<%d,%d>", a.Ci, a.Co);
+      case IG_GEMM256: IG_KERNEL(launch_gemm256<T>(a, c.gemm256, st), "conv_gemm256_kernel");
+      case IG_DMA:
+        switch (c.bn * 100 + c.bk) {
+          case 12864: IG_KERNEL((launch_dma<T, 128, 64, 2>(a, st)), "conv_igemm_dma_kernel<128,64,2>");
+          case 12832: IG_KERNEL((launch_dma<T, 128, 32, 3>(a, st)), "conv_igemm_dma_kernel<128,32,3>");
+          case 6432: IG_KERNEL((launch_dma<T, 64, 32, 3>(a, st)), "conv_igemm_dma_kernel<64,32,3>");
+          default: IG_KERNEL((launch_dma<T, 32, 64, 3>(a, st)), "conv_igemm_dma_kernel<32,64,3>");
+        }
+      default:
+        IG_KERNEL((c.bk == 64 ? launch_bn<T, 64>(a, st, c.bn) : launch_bn<T, 32>(a, st, c.bn)), "conv_igemm_kernel<bf16,%d,%d>", c.bn, c.bk);
+    }
+  }
+}
+#undef IG_KERNEL
+
+// ---- queries: one-line readers of choose ----
+#define GEOM_PARAMS int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int KH, int KW, int mul, int kmul, int off, int div, int up, int dtype
+#define GEOM_SHAPE(N) ConvShape{N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype}
+extern "C" int mi355_conv2d_igemm_variant(GEOM_PARAMS) { return (int)choose(GEOM_SHAPE(1)).shape_variant; }
+extern "C" int mi355_conv2d_igemm_variant_n(int N, GEOM_PARAMS) { return (int)choose(GEOM_SHAPE(N)).variant; }
+extern "C" int mi355_conv2d_igemm_stat_rows(int N, GEOM_PARAMS) { return choose(GEOM_SHAPE(N)).stat_rows; }
+extern "C" int mi355_conv2d_igemm_pool2_ok(int N, GEOM_PARAMS) { return choose(GEOM_SHAPE(N)).pool2; }
+/* output-channel tile (128 / 64 / 32) the LDS-DMA ring kernel (variant 1) / the generic kernel runs for N x Ho x Wo rows, Ci -> Co
+   channels: the rule choose applies, for callers that know the variant */
+extern "C" int mi355_conv2d_igemm_dma_tile(int N, int Ho, int Wo, int Ci, int Co) { return small_grid_tile_n((long long)N * Ho * Wo, Co, Ci % 64 == 0); }
+extern "C" int mi355_conv2d_igemm_generic_tile(int N, int Ho, int Wo, int Co) { return small_grid_tile_n((long long)N * Ho * Wo, Co, true); }
+extern "C" const char* mi355_conv2d_igemm_kernel_name(int N, GEOM_PARAMS) {
+  static thread_local char name[IG_NAME_LEN];
+  const ConvShape s = GEOM_SHAPE(N); const ConvChoice c = choose(s);
+  const int rc = dispatch_dtype(dtype, "conv2d_igemm_kernel_name", [&](auto tag) { return launch_or_name<decltype(tag)>(c, conv_args(s), nullptr, name); });
+  return rc == MI355_OK ? name : nullptr;
 }
 
 extern "C" int mi355_conv2d_igemm(const void* in, const void* wk, const float* bias, void* out, int N, int Hi, int Wi,
@@ -708,59 +764,21 @@ extern "C" int mi355_conv2d_igemm(const void* in, const void* wk, const float* b
                       (ldi * esz) % 16 == 0 && (ldo * esz) % 16 == 0,
                   "conv2d_igemm: pointers / channel strides must be 16-byte aligned");
   MI355_CHECK_ARG(Ci % (esz == 2 ? 32 : 16) == 0, "conv2d_igemm: Ci=%d must be a multiple of %d", Ci, esz == 2 ? 32 : 16);
-  // the halo / ping-pong / weight-stationary kernels address an image through a buffer descriptor with 32-bit lane offsets and a
-  // 2^31-byte range check (dma.hpp): an image of 2 GiB or more would be zero-filled silently — final_variant sends such shapes to
-  // the LDS-DMA ring kernel with its 64-bit addresses (judged on Ci, which the statistics-row query knows too; a channel STRIDE
-  // that alone pushes an image over the limit is refused below)
-  const IgemmVariant v = final_variant(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up, dtype);
-  MI355_CHECK_ARG(!halo_family(v) || image_fits_descriptor(Hi, Wi, ldi, esz),
+  const ConvShape shape = GEOM_SHAPE(N);
+  const ConvChoice c = choose(shape);
+  MI355_CHECK_ARG(!halo_family(c.variant) || image_fits_descriptor(Hi, Wi, ldi, esz),
                   "conv2d_igemm: an image of %d x %d pixels at a channel stride of %d is 2 GiB or more: beyond the 32-bit lane offsets of "
                   "the halo kernels' buffer descriptors", Hi, Wi, ldi);
-  MI355_CHECK_ARG(!stats || (stat_rows_of(v, N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up) > 0 && !(accumulate & 1)),
+  MI355_CHECK_ARG(!stats || (c.stat_rows > 0 && !(accumulate & 1)),
                   "conv2d_igemm: fused statistics are not available for this shape/dtype (mi355_conv2d_igemm_stat_rows == 0)");
-  ConvArgs a;
+  ConvArgs a = conv_args(shape);
   a.in = in; a.wk = wk; a.bias = bias; a.out = out;
-  a.N = N; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci; a.ldi = ldi;
-  a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.ldo = ldo;
-  a.KH = KH; a.KW = KW; a.mul = mul; a.kmul = kmul; a.off = off;
-  a.dshift = div == 1 ? 0 : (div == 2 ? 1 : 2);
-  a.up = up ? 1 : 0;
+  a.ldi = ldi; a.ldo = ldo;
   a.accumulate = accumulate & 1;
   a.relu = (accumulate >> 1) & 1;
   a.pool2 = (accumulate >> 2) & 1;
-  MI355_CHECK_ARG(!a.pool2 || ((v == IG_HALO_8x32 || v == IG_HALO_16x16 || v == IG_HALO_PP || v == IG_HALO_PP128 || v == IG_WS64 || v == IG_WS128) && !stats),
+  MI355_CHECK_ARG(!a.pool2 || (c.pool2 && !stats),
                   "conv2d_igemm: the 2x2-sum epilogue exists for the halo kernel only (mi355_conv2d_igemm_variant >= 2)");
   a.stats = stats;
-  a.M = N * Ho * Wo;
-  a.HoWo = Ho * Wo;
-  a.Hlog = up ? 2 * Hi : Hi;
-  a.Wlog = up ? 2 * Wi : Wi;
-  hipStream_t st = (hipStream_t)s;
-  const bool k64 = Ci % 64 == 0;
-  if (esz == 4) return launch_bn<float, 16>(a, st);      // (32-channel K tiles measured: +2 % on 128-wide tiles, -13 % on 64-wide ones)
-  return dispatch_dtype(dtype, "conv2d_igemm", [&](auto tag) -> int {
-    using T = decltype(tag);
-    if constexpr (sizeof(T) == 2) {
-      switch (v) {
-        case IG_HALO_PP: return launch_halo_pp<T>(a, st);
-        case IG_HALO_PP128: return launch_halo_pp128<T>(a, st);
-        case IG_WS64: return launch_ws<T, 64, 8>(a, st, device_cus());
-        case IG_WS128: return launch_ws<T, 128, 4>(a, st, device_cus());
-        case IG_HALO_8x32: return launch_halo_rw<T, 8, 32>(a, st);
-        case IG_HALO_16x16: return launch_halo_rw<T, 16, 16>(a, st);
-        case IG_STREAM1x1: return launch_stream1x1<T>(a, st);
-        case IG_GEMM256: return launch_gemm256<T>(a, gemm256_mode(N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up), st);
-        case IG_DMA:
-          // measured on MI355X (AttentionUNet shapes): the 2-deep BK=64 ring (2 workgroups/CU) wins for 128-wide tiles,
-          // the 3-deep BK=32 ring (3-4 workgroups/CU) for 64-wide tiles and for Ci % 64 != 0
-          switch (dma_tile_n(a.M, Ci, Co)) {
-            case 128: return k64 ? launch_dma<T, 128, 64, 2>(a, st) : launch_dma<T, 128, 32, 3>(a, st);
-            case 64: return launch_dma<T, 64, 32, 3>(a, st);
-            default: return launch_dma<T, 32, 64, 3>(a, st);
-          }
-        default: return k64 ? launch_bn<T, 64>(a, st) : launch_bn<T, 32>(a, st);
-      }
-    }
-    return MI355_ERR_UNSUPPORTED;
-  });
+  return dispatch_dtype(dtype, "conv2d_igemm", [&](auto tag) { return launch_or_name<decltype(tag)>(c, a, (hipStream_t)s, nullptr); });
 }

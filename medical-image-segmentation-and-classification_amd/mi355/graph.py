@@ -620,14 +620,13 @@ class Builder:
         nbytes = (x.N * x.H * x.W * x.C + x.N * Ho * Wo * Co + Co * k * k * x.C) * self.esz
         stat_part = None
         self._last_stat_rows = 0
+        geom = (x.N, x.H, x.W, x.C, Ho, Wo, Co, k, k, s, 1, -p, 1, 1 if up else 0)
         if stats and self.training:
-            rows = lib.mi355_conv2d_igemm_stat_rows(x.N, x.H, x.W, x.C, Ho, Wo, Co, k, k, s, 1, -p, 1, 1 if up else 0, self.code)
+            rows = lib.mi355_conv2d_igemm_stat_rows(*geom, self.code)
             if rows > 0:            # the kernel serving this shape folds the BatchNorm statistics into its epilogue
                 stat_part = self.ws_f32(rows * 2 * Co)
                 self._last_stat_rows = rows
-        self.fwd.append(Launch("mi355_conv2d_igemm", x, wf, bias, y, x.N, x.H, x.W, x.C, x.ld, Ho, Wo, Co, y.ld,
-                               k, k, s, 1, -p, 1, 1 if up else 0, 2 if relu else 0, stat_part, self.code, flops=flops, nbytes=nbytes,
-                               tag=self.igemm_tag(x.N, x.H, x.W, x.C, Ho, Wo, Co, k, s, 1, -p, 1, 1 if up else 0)))
+        self.fwd.append(self.igemm(x, wf, bias, y, geom, 2 if relu else 0, stat_part, flops=flops, nbytes=nbytes))
         y.needs_grad = x.needs_grad or self.param_grad(conv.weight)
         self._conv_uses[id(conv)] = self._conv_uses.get(id(conv), 0) + 1
 
@@ -654,29 +653,20 @@ class Builder:
             if conv.bias is not None and self.param_grad(conv.bias) and not bias_done:
                 self.bias_grad_from(dy, conv.bias)
             if x.needs_grad:
-                if up:
-                    acc = self.acc_flag(x)
-                    xg = self.grad_of(x)
-                    tag = self.igemm_tag(x.N, Ho, Wo, Co, 2 * x.H, 2 * x.W, x.C, k, 1, -1, p, s, 0)
-                    # (the launcher's own choice for THIS batch: the shape-level variant may fall back, by batch size, to the LDS-DMA ring
-                    #  kernel, which has no 2x2-sum epilogue)
-                    if lib.mi355_conv2d_igemm_variant_n(x.N, Ho, Wo, Co, 2 * x.H, 2 * x.W, x.C, k, k, 1, -1, p, s, 0, self.code) in (2, 3, 5, 6, 7, 8):
-                        # the data gradient lives on the up-sampled grid; its 2x2 sums go straight to the half-resolution
-                        # gradient in the kernel epilogue (no full-resolution temporary, no separate pass)
-                        self.bwd.append(Launch("mi355_conv2d_igemm", dy, wb, None, xg, x.N, Ho, Wo, Co, dy.ld, 2 * x.H, 2 * x.W,
-                                               x.C, xg.ld, k, k, 1, -1, p, s, 0, 4 | (1 if acc else 0), None, self.code, flops=flops,
-                                               nbytes=nbytes, tag=tag))
-                    else:
-                        tmp = self.new_tensor(x.N, 2 * x.H, 2 * x.W, x.C)
-                        self.bwd.append(Launch("mi355_conv2d_igemm", dy, wb, None, tmp, x.N, Ho, Wo, Co, dy.ld, 2 * x.H, 2 * x.W,
-                                               x.C, tmp.ld, k, k, 1, -1, p, s, 0, 0, None, self.code, flops=flops, nbytes=nbytes, tag=tag))
-                        self.bwd.append(Launch("mi355_upsample2_bwd", tmp, tmp.ld, xg, xg.ld, x.N, x.H, x.W, x.C, acc, self.code))
+                acc = self.acc_flag(x)
+                xg = self.grad_of(x)
+                hg, wg = (2 * x.H, 2 * x.W) if up else (x.H, x.W)      # the data gradient of an up-sampled input lives on the up-sampled grid
+                dgeom = (x.N, Ho, Wo, Co, hg, wg, x.C, k, k, 1, -1, p, s, 0)
+                if not up:
+                    self.bwd.append(self.igemm(dy, wb, None, xg, dgeom, acc, flops=flops, nbytes=nbytes))
+                elif lib.mi355_conv2d_igemm_pool2_ok(*dgeom, self.code):
+                    # its 2x2 sums go straight to the half-resolution gradient in the kernel epilogue: no full-resolution temporary, no separate
+                    # pass (the launcher's answer for THIS batch: by batch size it may fall back to the LDS-DMA ring kernel, which has none)
+                    self.bwd.append(self.igemm(dy, wb, None, xg, dgeom, 4 | (1 if acc else 0), flops=flops, nbytes=nbytes))
                 else:
-                    acc = self.acc_flag(x)
-                    xg = self.grad_of(x)
-                    self.bwd.append(Launch("mi355_conv2d_igemm", dy, wb, None, xg, x.N, Ho, Wo, Co, dy.ld, x.H, x.W, x.C,
-                                           xg.ld, k, k, 1, -1, p, s, 0, acc, None, self.code, flops=flops, nbytes=nbytes,
-                                           tag=self.igemm_tag(x.N, Ho, Wo, Co, x.H, x.W, x.C, k, 1, -1, p, s, 0)))
+                    tmp = self.new_tensor(x.N, hg, wg, x.C)
+                    self.bwd.append(self.igemm(dy, wb, None, tmp, dgeom, 0, flops=flops, nbytes=nbytes))
+                    self.bwd.append(Launch("mi355_upsample2_bwd", tmp, tmp.ld, xg, xg.ld, x.N, x.H, x.W, x.C, acc, self.code))
         return y, bwd
 
     def _emit_multi_wgrad(self, conv, pend, Ho, Wo, Co, k, up, flops, nbytes):
@@ -693,33 +683,20 @@ class Builder:
         ref, beta = self.pgrad(conv.weight)
         self.bwd.append(Launch("mi355_conv2d_wgrad_reduce", ws, splits, ref, Co, x0.C, conv.in_channels, k, k, 0, beta, side=True))
 
-    def igemm_tag(self, N, Hi, Wi, ci, Ho, Wo, co, k, mul, kmul, off, div, up):
-        """Name of the kernel mi355_conv2d_igemm runs for this launch: the launcher's own choice, batch-dependent fall-backs
-        included (mi355_conv2d_igemm_variant_n; csrc/conv_igemm.hip pick_variant / resolve_variant), so that bench.py's
-        per-kernel time and FLOP sums never mix two kernels under one name."""
-        bn = 128 if co % 128 == 0 else (64 if co % 64 == 0 else 32)
-        if self.dtype == torch.float32:
-            return f"conv_igemm_kernel<f32,{lib.mi355_conv2d_igemm_generic_tile(N, Ho, Wo, co)},16>"
-        v = lib.mi355_conv2d_igemm_variant_n(N, Hi, Wi, ci, Ho, Wo, co, k, k, mul, kmul, off, div, up, self.code)
-        k64 = ci % 64 == 0
-        if v == 0:
-            return f"conv_igemm_kernel<bf16,{lib.mi355_conv2d_igemm_generic_tile(N, Ho, Wo, co)},{64 if k64 else 32}>"
-        if v == 1:
-            bn = lib.mi355_conv2d_igemm_dma_tile(N, Ho, Wo, ci, co)      # (narrower than Co allows when the grid would be small)
-            if bn == 128:
-                return "conv_igemm_dma_kernel<128,64,2>" if k64 else "conv_igemm_dma_kernel<128,32,3>"
-            return "conv_igemm_dma_kernel<64,32,3>" if bn == 64 else "conv_igemm_dma_kernel<32,64,3>"
-        return {2: "conv3x3_halo_rw_kernel<8,32>", 3: "conv3x3_halo_rw_kernel<16,16>", 4: f"conv1x1_stream_kernel<{ci},{co}>",
-                5: "conv3x3_halo_pp_kernel", 6: "conv3x3_halo_pp128_kernel", 7: "conv3x3_ws_kernel<64,8>", 8: "conv3x3_ws_kernel<128,4>",
-                9: "conv_gemm256_kernel"}[v]
+    def igemm(self, x, w, bias, out, geom, flags=0, stats=None, **kw):
+        """One mi355_conv2d_igemm launch from ``geom`` = (N, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, mul, kmul, off, div, up), the tuple the
+        library's queries take too, tagged with the kernel the launcher runs for it."""
+        return Launch("mi355_conv2d_igemm", x, w, bias, out, *geom[:4], x.ld, *geom[4:7], out.ld, *geom[7:], flags, stats, self.code,
+                      tag=self.igemm_tag(geom), **kw)
+
+    def igemm_tag(self, geom):
+        """Name of the kernel mi355_conv2d_igemm runs for this launch: the launcher's own choice, batch-dependent fall-backs included
+        (csrc/conv_igemm.hip: choose, launch_or_name), so that bench.py's per-kernel sums never mix two kernels under one name."""
+        return lib.mi355_conv2d_igemm_kernel_name(*geom, self.code).decode()
 
     def wgrad_tag(self, co, ci, k=1, s=1, Ho=0, Wo=0, N=0, p=None):
-        """Name of the kernel mi355_conv2d_wgrad runs: the launcher's own choice (mi355_conv2d_wgrad_variant)."""
-        t = "f32" if self.dtype == torch.float32 else "bf16"       # (the fp16 build runs the same variants as bf16)
-        v = lib.mi355_conv2d_wgrad_variant(N, Ho, Wo, k, k, s, (k // 2) if p is None else p, self.code) if t == "bf16" else 0
-        if v:
-            return "wgrad3x3_halo8_kernel" if v >= 3 else "wgrad3x3_halo_kernel"
-        return f"conv_wgrad_kernel<{t},{128 if co % 128 == 0 else 64},{128 if ci % 128 == 0 else 64}>"
+        """Name of the kernel mi355_conv2d_wgrad runs: the launcher's own choice (csrc/conv_wgrad.hip)."""
+        return lib.mi355_conv2d_wgrad_kernel_name(N, Ho, Wo, ci, co, k, k, s, (k // 2) if p is None else p, self.code).decode()
 
     def wgrad_cus(self, N, Ho, Wo, ci, co, k, s, p, splits):
         """Share of the 256 CUs a weight-gradient launch is sized for: the eight-wave nine-tap kernel's workgroups own their CU
@@ -994,9 +971,7 @@ class Builder:
         y = out if out is not None else self.new_tensor(x.N, Ho, Wo, Co)
         flops = 2 * x.N * x.H * x.W * Ci * Co * k * k
         nbytes = (x.N * x.H * x.W * Ci + x.N * Ho * Wo * Co + Ci * Co * k * k) * self.esz
-        self.fwd.append(Launch("mi355_conv2d_igemm", x, wf, mod.bias, y, x.N, x.H, x.W, Ci, x.ld, Ho, Wo, Co, y.ld, k, k,
-                               1, -1, 0, s, 0, 0, None, self.code, flops=flops, nbytes=nbytes,
-                               tag=self.igemm_tag(x.N, x.H, x.W, Ci, Ho, Wo, Co, k, 1, -1, 0, s, 0)))
+        self.fwd.append(self.igemm(x, wf, mod.bias, y, (x.N, x.H, x.W, Ci, Ho, Wo, Co, k, k, 1, -1, 0, s, 0), flops=flops, nbytes=nbytes))
         y.needs_grad = x.needs_grad or self.param_grad(mod.weight)
 
         def rule():
@@ -1017,9 +992,7 @@ class Builder:
             if x.needs_grad:
                 acc = self.acc_flag(x)
                 xg = self.grad_of(x)
-                self.bwd.append(Launch("mi355_conv2d_igemm", dy, wb, None, xg, x.N, Ho, Wo, Co, dy.ld, x.H, x.W, Ci, xg.ld,
-                                       k, k, s, 1, 0, 1, 0, acc, None, self.code, flops=flops, nbytes=nbytes,
-                                       tag=self.igemm_tag(x.N, Ho, Wo, Co, x.H, x.W, Ci, k, s, 1, 0, 1, 0)))
+                self.bwd.append(self.igemm(dy, wb, None, xg, (x.N, Ho, Wo, Co, x.H, x.W, Ci, k, k, s, 1, 0, 1, 0), acc, flops=flops, nbytes=nbytes))
         self.rule(rule)
         return y
 
