@@ -469,6 +469,29 @@ int mi355_surface_ws_ints(int B, int H, int W);
 int mi355_surface_distances(const float* pred, const float* target, int B, int H, int W, int is_logit, float thr, int q,
                             int tol2, int32_t* ws, long long ws_ints, int32_t* out_i, double* out_d, mi355_stream_t s);
 
+/* ---- connected components of a mask: clean-up and lesion statistics (nothing in the reference, which overlays the thresholded
+ * mask as it is) --------------------------------------------------------------------------------------------------------- */
+/* Per sample b of [B][H][W] fp32 maps, binarised exactly as mi355_seg_counts does (m = prob > thr), all in integers and equal to
+ * scipy.ndimage:
+ *   fill_holes (0 = off, 4 or 8): background components under that connectivity that do not touch the image frame become foreground
+ *     (binary_fill_holes with generate_binary_structure(2, 1 or 2));
+ *   the components of the filled mask under `connectivity` (4 or 8) are numbered 1..n by increasing `first`, the smallest linear
+ *     index y W + x among a component's pixels (ndimage.label's numbering), and ranked by (area descending, first ascending);
+ *   a component is kept iff area >= min_area and (keep_largest == 0 or its rank < keep_largest).
+ *   mask_out[b][H][W]   uint8: 255 on kept components, 0 elsewhere
+ *   labels_out[b][H][W] int32 or NULL: the numbering, whatever the filter keeps
+ *   out_i[b][0..8)      foreground pixels after thresholding, pixels added by hole filling, components, kept components, foreground
+ *                       pixels of mask_out, largest area of any component, rows reported = min(kept, max_report), status (0 = ok)
+ *   out_c[b][max_report][8]  the kept components in rank order: area, first, y0, x0, y1, x1 (inclusive box), sum of y, sum of x;
+ *                       unused rows zero
+ * 1 <= H, W <= 1024, 0 <= max_report <= 16.  `ws` = mi355_components_ws_ints(B, H, W) int32 elements of scratch (-1 + last_error
+ * when the shape is unsupported), 16-byte aligned.  Integer atomics only: the same input gives the same bytes.  No loop waits for
+ * another workgroup, and every union-find loop is bounded: status != 0 reports a bound that was hit. */
+int mi355_components_ws_ints(int B, int H, int W);
+int mi355_components(const float* src, int B, int H, int W, int is_logit, float thr, int connectivity, int fill_holes, int min_area,
+                     int keep_largest, int max_report, int32_t* ws, long long ws_ints, uint8_t* mask_out, int32_t* labels_out,
+                     int32_t* out_i, int32_t* out_c, mi355_stream_t s);
+
 /* ---- launch-plan replay: the per-batch host loop of utils/helpers.py:317-342 (model(x) ... loss.backward()) as ONE call ---- */
 /* A plan is a table of pre-resolved launches of the entry points above: `name`, its arguments as 64-bit slots in prototype
  * order INCLUDING the trailing stream (pointers and integers by value, floats as their IEEE-754 bit pattern in the low 32

@@ -10,7 +10,8 @@ padded to a multiple of ``bucket`` so that at most B / bucket launch plans ever 
 ``predict`` takes the already normalised tensor (``val_transform`` output) and returns the masks (with ``explain=True``
 also the Grad-CAM map of every sample's predicted class, utils/explain.py).  ``process_images`` is ``process_image``'s
 per-file result — the red overlay at the file's own size (:399-413, mi355_overlay_mask) and the analysis text (:391-417) —
-for a list of PNG files, run as one batch."""
+for a list of PNG files, run as one batch.  ``postprocess`` (a utils.postprocess.MaskPostprocess; nothing in the reference) cleans
+the masks by connected components on the device before they are overlaid and adds the lesion count and area to the text."""
 from __future__ import annotations
 
 import torch
@@ -21,11 +22,12 @@ CLASSES = ["COVID", "Healthy", "Non-COVID"]          # pipeline.py:22
 
 
 class JointPipeline:
-    def __init__(self, classification_model, segmentation_model, device="cuda", classes=CLASSES, positive="COVID", bucket=4):
+    def __init__(self, classification_model, segmentation_model, device="cuda", classes=CLASSES, positive="COVID", bucket=4, postprocess=None):
         self.device = torch.device(device)
         self.classes = list(classes)
         self.keep = self.classes.index(positive)
         self.bucket = int(bucket)
+        self.postprocess = postprocess
         self.classification_model = classification_model.to(self.device).eval()
         self.segmentation_model = None if segmentation_model is None else segmentation_model.to(self.device).eval()
 
@@ -35,7 +37,9 @@ class JointPipeline:
         ``pred`` int32 [B] class index, ``confidence`` float [B] in percent, ``masks`` uint8 [B,H,W] (0 / 255; all zero
         where no segmentation ran), ``segmented`` bool [B].  ``explain``: also ``cam`` float32 [B,H,W] (and ``cam_lowres`` at
         the feature-map size), the Grad-CAM of each sample's predicted class; the logits then come from the classifier's explain
-        plan, whose forward is the eval forward: every other output is the same, bit for bit."""
+        plan, whose forward is the eval forward: every other output is the same, bit for bit.  With a ``postprocess``: ``masks`` are
+        the cleaned masks, ``masks_raw`` the thresholded ones, ``n_lesions`` int32 [B] and ``area_percent`` float64 [B] the kept
+        components and their share of the image, ``lesions`` int32 [B,max_report,8] their rows (utils/postprocess.py)."""
         x = x.to(self.device, dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
         cams = None
@@ -66,6 +70,10 @@ class JointPipeline:
         elif self.segmentation_model is None:
             segmented = torch.zeros_like(segmented)
         out = {"pred": pred, "confidence": conf, "masks": masks, "segmented": segmented}
+        if self.postprocess is not None:
+            clean = self.postprocess(masks)            # 0 / 255 against 0.5; rows without a segmentation are empty and stay so
+            out.update(masks=clean["mask"], masks_raw=masks, n_lesions=clean["n_kept"], area_percent=clean["area_percent"],
+                       lesions=clean["out_c"])
         if cams is not None:
             out["cam"], out["cam_lowres"] = cams["cam"], cams["cam_lowres"]
         return out
@@ -110,6 +118,7 @@ class JointPipeline:
             xs.append(tf(im))
         r = self.predict(torch.cat(xs) if len(xs) > 1 else xs[0], explain=explain)
         pred, conf = r["pred"].cpu(), r["confidence"].cpu()
+        lesions = (r["n_lesions"].cpu(), r["area_percent"].cpu()) if "n_lesions" in r else None
         positive = self.classes[self.keep]
         results = [None] * len(paths)
         row = 0
@@ -129,6 +138,8 @@ class JointPipeline:
                 elif red is not None:
                     output_img = red[j]
                     text += "\nInfection areas have been highlighted in red (segmentation model)."
+                    if lesions is not None:
+                        text += f"\nLesions: {int(lesions[0][row + j])} (area {float(lesions[1][row + j]):.2f}% of the image)."
                 else:
                     text += "\nWARNING: Segmentation model failed to load. Cannot highlight infection areas."
                 results[i] = (prediction, confidence, output_img, text) + ((heat[j],) if explain else ())
