@@ -369,6 +369,31 @@ int mi355_seg_loss_fwd(const float* z, const float* t, int B, long long per, flo
                        float smooth, int per_sample, float* partial, float* state, float* loss, mi355_stream_t s);
 int mi355_seg_loss_bwd(const float* z, const float* t, int B, long long per, float bce_weight, const float* state,
                        const float* gscale, float* dz, mi355_stream_t s);
+/* Boundary loss (Kervadec et al., MIDL 2019; nothing in the reference): the mean of sigmoid(z) * phi, phi the signed
+ * Euclidean distance map of the ground truth, rebuilt on the device for every batch.
+ *   mi355_signed_dist2: target [B][H][W] fp32, binarised as target > thr -> sd2 int32 [B][H][W]: +min(dy^2 + dx^2) over
+ *     the sample's foreground pixels at an outside pixel (>= 1), -min(dy^2 + dx^2) over its background pixels at an
+ *     inside pixel (<= -1), 0 everywhere for a sample without foreground or without background (no boundary).  Pixels
+ *     outside the image are NOT background (unlike the border rule of mi355_surface_distances).  Integer arithmetic,
+ *     exact.  1 <= H, W <= 1024, 0 < B <= 65535; `ws` = mi355_sdist_ws_ints(B, H, W) int32 elements of scratch (-1 +
+ *     last_error when the shape is out of range); ws and sd2 must not overlap.  Two launches, no allocation, no sync.
+ *   mi355_boundary_loss_rows: floats `partial` must hold; a function of (B, per) alone.
+ *   mi355_boundary_loss_fwd: with phi = sqrt(sd2) (sd2 > 0), -(sqrt(-sd2) - 1) (sd2 < 0), 0 (sd2 = 0), on fp32 logits
+ *     z [B][per]:  loss[0] = (base ? base[0] : 0) + weight / (B per) * sum_i sigmoid(z_i) phi_i.  `base` is a device
+ *     scalar (the regional loss the term is added to) or NULL.  One pass (16-byte accesses when per % 4 == 0 and z, sd2
+ *     are 16-byte aligned) and a one-workgroup fold in double; no floating-point atomics, bit-reproducible.
+ *   mi355_boundary_loss_bwd: dz_i (+)= gscale[0] * weight / (B per) * phi_i p_i (1 - p_i); gscale NULL = 1;
+ *     accumulate != 0 adds the rounded term to what dz holds (another criterion's gradient in the same buffer),
+ *     accumulate = 0 overwrites.
+ * weight >= 0, B <= 65535. */
+int mi355_sdist_ws_ints(int B, int H, int W);
+int mi355_signed_dist2(const float* target, int B, int H, int W, float thr, int32_t* ws, long long ws_ints,
+                       int32_t* sd2, mi355_stream_t s);
+int mi355_boundary_loss_rows(int B, long long per);
+int mi355_boundary_loss_fwd(const float* z, const int32_t* sd2, int B, long long per, float weight, const float* base,
+                            float* partial, float* loss, mi355_stream_t s);
+int mi355_boundary_loss_bwd(const float* z, const int32_t* sd2, int B, long long per, float weight, const float* gscale,
+                            int accumulate, float* dz, mi355_stream_t s);
 
 /* ---- optimiser on flat fp32 buffers (utils/helpers.py:251,304,332-336) ---------------------- */
 /* sumsq partials of a flat gradient buffer; nblocks = mi355_rowreduce_blocks(n). */

@@ -113,6 +113,155 @@ class DiceLoss(CombinedLoss):
         super().__init__(0.0, 1.0, smooth, per_sample)
 
 
+def _signed_dist2(target, threshold=0.5):
+    """mi355_signed_dist2 on a contiguous fp32 device tensor [B, H, W] -> int32 [B, H, W] (csrc/boundary.hip): the signed squared
+    Euclidean distance map of ``target > threshold``.  No host round trip."""
+    B, H, W = target.shape
+    n = lib.raw("mi355_sdist_ws_ints")(B, H, W)
+    if n <= 0:
+        raise RuntimeError(f"mi355_sdist_ws_ints failed: {lib.raw('mi355_last_error')().decode()}")
+    ws = torch.empty(n, dtype=torch.int32, device=target.device)
+    sd2 = torch.empty(B, H, W, dtype=torch.int32, device=target.device)
+    lib.mi355_signed_dist2(target, B, H, W, float(threshold), ws, n, sd2)
+    return sd2
+
+
+class _RegionBoundaryFn(torch.autograd.Function):
+    """region + boundary as ONE autograd node.  Every mi355 criterion's backward returns the plan's ``dout`` buffer, so two nodes
+    would hand autograd two views of one buffer, the second launch having overwritten the first ("Boundary loss"): here
+    the regional backward writes ``dz`` and the boundary backward accumulates into it.  ``region`` = (bce_weight, dice_weight,
+    smooth, per_sample) or None for the boundary term alone; next to a regional loss a boundary weight of 0 launches nothing more
+    than CombinedLoss does."""
+
+    @staticmethod
+    def forward(ctx, out, target, plan, region, boundary_weight, threshold):
+        if out.dim() == 4 and out.shape[1] == 1:
+            B, H, W = out.shape[0], out.shape[2], out.shape[3]
+        elif out.dim() == 3:
+            B, H, W = out.shape
+        else:
+            raise ValueError(f"the boundary loss is defined for one-channel logits [B,1,H,W] or [B,H,W], got {tuple(out.shape)}")
+        if target.dtype != torch.float32 or not target.is_contiguous():
+            target = target.float().contiguous()
+        if target.numel() != out.numel():
+            raise ValueError(f"target size {tuple(target.shape)} must match input size {tuple(out.shape)}")
+        o = out.detach()
+        if not o.is_contiguous():
+            o = o.contiguous()
+        per = H * W
+        rows_r = 0
+        if region is not None:
+            rows_r = lib.mi355_seg_loss_rows(B, per)
+            if rows_r <= 0:
+                raise RuntimeError(f"mi355_seg_loss_rows failed: {lib.raw('mi355_last_error')().decode()}")
+        run_b = boundary_weight > 0 or region is None
+        rows_b = 0
+        if run_b:
+            rows_b = lib.mi355_boundary_loss_rows(B, per)
+            if rows_b <= 0:
+                raise RuntimeError(f"mi355_boundary_loss_rows failed: {lib.raw('mi355_last_error')().decode()}")
+        # one buffer: [rows_r x 4 regional partial sums | (a_b, c_b) per sample | regional loss, loss | boundary partial sums]
+        buf = torch.empty(rows_r * 4 + 2 * B + 2 + rows_b, dtype=torch.float32, device=out.device)
+        partial, state = buf[: rows_r * 4], buf[rows_r * 4: rows_r * 4 + 2 * B]
+        base, loss, bpartial = buf[rows_r * 4 + 2 * B:][:1], buf[rows_r * 4 + 2 * B + 1:][:1], buf[rows_r * 4 + 2 * B + 2:]
+        if region is not None:
+            bw, dw, smooth, per_sample = region
+            lib.mi355_seg_loss_fwd(o, target, B, per, bw, dw, smooth, 1 if per_sample else 0, partial, state,
+                                   base if run_b else loss)
+        sd2 = None
+        if run_b:
+            sd2 = _signed_dist2(target.view(B, H, W), threshold)
+            lib.mi355_boundary_loss_fwd(o, sd2, B, per, boundary_weight, base if region is not None else None, bpartial, loss)
+        ctx.o, ctx.t, ctx.plan, ctx.state, ctx.sd2 = o, target, plan, state, sd2
+        ctx.region, ctx.w, ctx.run_b = region, boundary_weight, run_b
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t, plan = ctx.o, ctx.t, ctx.plan
+        n = o.numel()
+        B = o.shape[0]
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        if ctx.region is not None:
+            lib.mi355_seg_loss_bwd(o, t, B, n // B, ctx.region[0], ctx.state, gs, dz)
+        if ctx.run_b:
+            lib.mi355_boundary_loss_bwd(o, ctx.sd2, B, n // B, ctx.w, gs, 1 if ctx.region is not None else 0, dz)
+        return dz[:n].view(o.shape), None, None, None, None, None
+
+
+class BoundaryLoss(nn.Module):
+    """weight * mean(sigmoid(logits) * phi), phi the signed Euclidean distance map of ``target > threshold`` (Kervadec et al., MIDL
+    2019: negative inside the mask, positive outside, zero for a sample without a boundary), built on the device for every batch
+    (csrc/boundary.hip).  Logits [B,1,H,W] or [B,H,W], H, W <= 1024.  Deterministic.  To add it to a regional loss use
+    RegionBoundaryLoss: the sum of two mi355 criteria is not a valid loss (both write their gradient into the plan's ``dout``)."""
+
+    def __init__(self, weight=1.0, threshold=0.5):
+        super().__init__()
+        if weight < 0:
+            raise ValueError(f"weight must not be negative ({weight})")
+        self.weight, self.threshold = float(weight), float(threshold)
+
+    def forward(self, out, target):
+        if out.dtype != torch.float32:
+            out = out.float()
+        return _RegionBoundaryFn.apply(out, target, getattr(out, "_mi355_plan", None), None, self.weight, self.threshold)
+
+    def extra_repr(self):
+        return f"weight={self.weight}, threshold={self.threshold}"
+
+
+class RegionBoundaryLoss(nn.Module):
+    """CombinedLoss(bce_weight, dice_weight, smooth, per_sample) plus the boundary loss, as one autograd node.
+
+    ``schedule="constant"``: region + boundary_weight * boundary.  ``schedule="rebalance"`` (Kervadec): with
+    a = min(boundary_weight + epoch * step, max_weight), (1 - a) * region + a * boundary; ``train()`` calls
+    ``on_epoch(epoch_index, epochs)`` at the start of every epoch (epoch_index from 0).  The factor (1 - a) goes into the two regional
+    weights handed to the kernels: no extra pass."""
+
+    SCHEDULES = ("constant", "rebalance")
+
+    def __init__(self, bce_weight=0.5, dice_weight=0.5, boundary_weight=0.01, smooth=1.0, per_sample=False, schedule="constant",
+                 step=0.01, max_weight=0.99, threshold=0.5):
+        super().__init__()
+        if bce_weight < 0 or dice_weight < 0 or boundary_weight < 0 or smooth < 0:
+            raise ValueError(f"bce_weight, dice_weight, boundary_weight and smooth must not be negative "
+                             f"({bce_weight}, {dice_weight}, {boundary_weight}, {smooth})")
+        if schedule not in self.SCHEDULES:
+            raise ValueError(f"schedule must be one of {self.SCHEDULES}, got {schedule!r}")
+        if step < 0 or not 0 <= max_weight <= 1:
+            raise ValueError(f"step must not be negative and max_weight must lie in [0, 1] ({step}, {max_weight})")
+        if schedule == "rebalance" and boundary_weight > 1:
+            raise ValueError(f"schedule='rebalance' mixes (1 - a) * region + a * boundary: boundary_weight <= 1 expected ({boundary_weight})")
+        self.bce_weight, self.dice_weight, self.boundary_weight = float(bce_weight), float(dice_weight), float(boundary_weight)
+        self.smooth, self.per_sample, self.threshold = float(smooth), bool(per_sample), float(threshold)
+        self.schedule, self.step, self.max_weight = schedule, float(step), float(max_weight)
+        self.epoch = 0
+
+    def on_epoch(self, epoch, epochs=None):
+        self.epoch = int(epoch)
+
+    def current_weights(self):
+        """(factor of the regional loss, factor of the boundary loss) at the current epoch."""
+        if self.schedule == "constant":
+            return 1.0, self.boundary_weight
+        a = min(self.boundary_weight + self.epoch * self.step, self.max_weight)
+        return 1.0 - a, a
+
+    def forward(self, out, target):
+        if out.dtype != torch.float32:
+            out = out.float()
+        r, a = self.current_weights()
+        region = (r * self.bce_weight, r * self.dice_weight, self.smooth, self.per_sample)
+        return _RegionBoundaryFn.apply(out, target, getattr(out, "_mi355_plan", None), region, a, self.threshold)
+
+    def extra_repr(self):
+        return (f"bce_weight={self.bce_weight}, dice_weight={self.dice_weight}, boundary_weight={self.boundary_weight}, "
+                f"smooth={self.smooth}, per_sample={self.per_sample}, schedule={self.schedule!r}, step={self.step}, "
+                f"max_weight={self.max_weight}")
+
+
 class _CEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, out, target, smoothing, plan):

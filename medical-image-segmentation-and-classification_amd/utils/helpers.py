@@ -165,6 +165,8 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
     t0 = time.time()
 
     for epoch in range(1, epochs + 1):
+        if hasattr(criterion, "on_epoch"):
+            criterion.on_epoch(epoch - 1, epochs)     # epoch-dependent loss weights (mnn.RegionBoundaryLoss), index from 0
         if not seg and epoch == STAGE1 + 1:
             say(f"\n--- STAGE 2: Full Fine-Tuning (Epochs {epoch}-{epochs}) ---")
             for p in model.parameters():

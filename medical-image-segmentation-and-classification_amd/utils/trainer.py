@@ -8,6 +8,7 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
 
     python utils/trainer.py --task seg --model attentionunet --epochs 2 --samples 64
     python utils/trainer.py --task seg --model r2attunet --seg-loss bce_dice --bce-weight 0.5 --dice-weight 0.5
+    python utils/trainer.py --task seg --model attentionunet --seg-loss bce_dice --boundary-weight 0.01 --boundary-schedule rebalance
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -71,11 +72,24 @@ def build_parser():
     ap.add_argument("--bce-weight", type=float, default=0.5, help="bce_dice: weight of the BCE term")
     ap.add_argument("--dice-weight", type=float, default=0.5, help="bce_dice: weight of the Dice term")
     ap.add_argument("--dice-per-sample", action="store_true", help="Dice term per image, averaged over the batch (default: over the whole batch)")
+    ap.add_argument("--boundary-weight", type=float, default=0.0,
+                    help="weight of the boundary loss (Kervadec et al. 2019) added to --seg-loss; 0 = off")
+    ap.add_argument("--boundary-schedule", choices=["constant", "rebalance"], default="constant",
+                    help="constant: region + w * boundary; rebalance: (1 - a) * region + a * boundary, a = min(w + epoch * step, 0.99)")
+    ap.add_argument("--boundary-step", type=float, default=0.01, help="rebalance: growth of the boundary weight per epoch")
     return ap
 
 
 def seg_criterion(args):
-    """The loss module --seg-loss asks for; None = train()'s own default (BCEWithLogits)."""
+    """The loss module --seg-loss asks for; None = train()'s own default (BCEWithLogits).  With --boundary-weight > 0 it is that
+    regional loss plus the boundary loss, as one criterion (mi355.nn.RegionBoundaryLoss)."""
+    if args.boundary_weight < 0:
+        raise ValueError(f"--boundary-weight must not be negative ({args.boundary_weight})")
+    if args.boundary_weight > 0:
+        from mi355 import nn as mnn
+        bw, dw = {"bce": (1.0, 0.0), "dice": (0.0, 1.0), "bce_dice": (args.bce_weight, args.dice_weight)}[args.seg_loss]
+        return mnn.RegionBoundaryLoss(bw, dw, args.boundary_weight, per_sample=args.dice_per_sample, schedule=args.boundary_schedule,
+                                      step=args.boundary_step)
     if args.seg_loss == "bce":
         return None
     from mi355 import nn as mnn
