@@ -433,6 +433,22 @@ int mi355_warp_u8(const uint8_t* src, int N, int Hs, int Ws, int C, const float*
 int mi355_normalize_u8(const uint8_t* src, int N, int H, int W, int C, const float* bc, const float* mean, const float* stdv,
                        float* out, mi355_stream_t s);
 
+/* ---- elastic deformation (Simard et al. 2003; A.ElasticTransform — not in the reference's pipelines, an optional stage of ours) ---- */
+/* Separable 1-D correlation of `planes` fp32 planes [planes][H][W], along H then along W (scipy.ndimage's axis order):
+ * per axis out[i] = sum_{k = 0 .. 2 radius} taps[k] * ext(in)[i + k - radius], ext = scipy's mode='reflect' (half-sample
+ * symmetric, d c b a | a b c d | d c b a, period 2n: radius may exceed the extent many times).  taps: 2 radius + 1 fp32 values on
+ * the device, any values (the kernel knows nothing about Gaussians); 0 <= radius <= 1024; tmp: scratch of planes H W floats (holds
+ * the H pass); src, tmp and dst must differ.  fp32 FMA chain in ascending k per output, no atomics: bit-reproducible.  Two launches. */
+int mi355_sepblur_reflect_f32(const float* src, int planes, int H, int W, const float* taps, int radius, float* tmp, float* dst,
+                              mi355_stream_t s);
+/* mi355_warp_u8 with a displacement field: field [N][2][H][W] fp32 at destination resolution (plane 0 dx, plane 1 dy), alpha [N]
+ * fp32.  For destination pixel (x, y) of sample n, in fp32 without contraction and in this order,
+ *   px = x + alpha[n] * dx(x, y);  py = y + alpha[n] * dy(x, y);  sx = m0 * px + m1 * py + m2;  sy = m3 * px + m4 * py + m5,
+ * then mi355_warp_u8's sampling of (sx, sy) (the same device function): out(p) = src(M (p + alpha d(p))), the elastic displacement
+ * applied after the affine map in ONE interpolation.  alpha[n] = 0 gives mi355_warp_u8's bytes.  src and dst must differ. */
+int mi355_warp_field_u8(const uint8_t* src, int N, int Hs, int Ws, int C, const float* m, const float* field, const float* alpha,
+                        uint8_t* dst, int H, int W, int nearest, int reflect, mi355_stream_t s);
+
 /* ---- PNG files -> uint8 batch on the host (utils/dataset.py:55,101-102: PIL Image.open(path).convert("RGB" | "L")) ----------- */
 /* Header fields of a PNG held in memory.  MI355_ERR_UNSUPPORTED (fields still filled) for an unknown interlace method or more
  * than 32768 pixels per side. */

@@ -8,12 +8,7 @@
 //                  A.Normalize ((v / 255 - mean) / std) + ToTensorV2 (HWC -> CHW fp32); masks: v / 255
 // HBM-bound and tiny next to a train step (a 32-image batch is 6 MB); one thread per output pixel.
 #include "common.hpp"
-
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-  return i;
-}
+#include "warp_sample.hpp"
 
 // m: [N][6] row-major 2x3, maps dst pixel (x, y) to src coordinates: sx = m0*x + m1*y + m2, sy = m3*x + m4*y + m5
 __global__ void warp_u8_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, const float* __restrict__ m, uint8_t* __restrict__ dst,
@@ -26,26 +21,7 @@ __global__ void warp_u8_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, 
     const int n = (int)(r / H);
     const float* mm = m + (size_t)n * 6;
     const float sx = mm[0] * x + mm[1] * y + mm[2], sy = mm[3] * x + mm[4] * y + mm[5];
-    const uint8_t* s = src + (size_t)n * Hs * Ws * C;
-    uint8_t* d = dst + ((size_t)(n * H + y) * W + x) * C;
-    auto at = [&](int yy, int xx, int c) -> float {
-      if (reflect) { yy = reflect101(yy, Hs); xx = reflect101(xx, Ws); }
-      else { yy = min(max(yy, 0), Hs - 1); xx = min(max(xx, 0), Ws - 1); }
-      return (float)s[((size_t)yy * Ws + xx) * C + c];
-    };
-    if (nearest) {
-      const int xi = (int)floorf(sx + 0.5f), yi = (int)floorf(sy + 0.5f);
-      for (int c = 0; c < C; ++c) d[c] = (uint8_t)at(yi, xi, c);
-    } else {
-      const float fx = floorf(sx), fy = floorf(sy);
-      const int x0 = (int)fx, y0 = (int)fy;
-      const float ax = sx - fx, ay = sy - fy;
-      for (int c = 0; c < C; ++c) {
-        const float top = at(y0, x0, c) * (1.f - ax) + at(y0, x0 + 1, c) * ax;
-        const float bot = at(y0 + 1, x0, c) * (1.f - ax) + at(y0 + 1, x0 + 1, c) * ax;
-        d[c] = (uint8_t)fminf(fmaxf(rintf(top * (1.f - ay) + bot * ay), 0.f), 255.f);
-      }
-    }
+    warp_sample_u8(src + (size_t)n * Hs * Ws * C, Hs, Ws, C, sx, sy, dst + ((size_t)(n * H + y) * W + x) * C, nearest, reflect);
   }
 }
 

@@ -5,7 +5,14 @@ utils/dataset.py:120-126).  Four CPU DataLoader workers running those per image 
 1500 images/s; here a 32-image batch costs a few launches over 6 MB.
 
 The random draws (angle, scale, shift, flip, brightness / contrast — same ranges and probabilities as the reference)
-come from a ``torch.Generator`` on the host and travel as a [N, 6] matrix and a [N, 2] vector."""
+come from a ``torch.Generator`` on the host and travel as a [N, 6] matrix and a [N, 2] vector.
+
+``elastic=(alpha, sigma, p)`` adds ``A.ElasticTransform`` (Simard et al. 2003; not in the reference's pipelines, off by default) to
+the train transforms: per batch one uniform noise field drawn on the device, smoothed by a Gaussian of ``sigma`` pixels
+(utils/elastic.py, csrc/elastic.hip) and added, times ``alpha`` for the samples chosen with probability ``p`` and times 0 for the
+others, to the sampling coordinate of the ShiftScaleRotate warp: ``out(q) = src(M (q + alpha d(q)))``, one interpolation for both,
+the same field for image (bilinear) and mask (nearest).  Its draws come from generators of their own, so ``elastic=None`` leaves
+every launch and every draw of a given seed as it was."""
 from __future__ import annotations
 
 import math
@@ -13,6 +20,7 @@ import math
 import torch
 
 from mi355.lib import lib
+from utils import elastic as _elastic
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # trainer.py:48-49
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -37,11 +45,20 @@ def shift_scale_rotate_matrix(h, w, angle_deg, scale, dx, dy, hflip=False):
 
 class SegBatchTransform:
     """train_seg_transform / val_seg_transform (trainer.py:83-112) for a batch: ``(images uint8 [N,Hs,Ws,3], masks uint8
-    [N,Hs,Ws]) -> (x float32 [N,3,S,S] normalised, y float32 [N,1,S,S] in {0,1})`` on the GPU."""
+    [N,Hs,Ws]) -> (x float32 [N,3,S,S] normalised, y float32 [N,1,S,S] in {0,1})`` on the GPU.  ``params`` fixes the draws of a
+    train-mode call: ``(mats, bcs)`` as ``draw`` returns them, plus, with ``elastic=(alpha, sigma, p)``, an optional third element
+    ``(noise [N,2,S,S], alphas [N])`` as ``draw_elastic`` returns it."""
 
-    def __init__(self, size=256, train=False, seed=0, device="cuda"):
+    def __init__(self, size=256, train=False, seed=0, device="cuda", elastic=None):
         self.size, self.train, self.device = size, train, torch.device(device)
         self.gen = torch.Generator().manual_seed(seed)
+        self.elastic = None
+        if elastic is not None:
+            if len(elastic) != 3:
+                raise ValueError(f"elastic must be None or (alpha, sigma, p), got {elastic!r}")
+            self.elastic = _elastic.check_elastic(*elastic)
+            self.elastic_gen = torch.Generator().manual_seed(seed)                  # which samples: host; self.gen is not touched
+            self.noise_gen = torch.Generator(device=self.device).manual_seed(seed)  # the noise field: drawn where it is used
         self.mean = torch.tensor(IMAGENET_MEAN, device=self.device)
         self.std = torch.tensor(IMAGENET_STD, device=self.device)
 
@@ -60,6 +77,14 @@ class SegBatchTransform:
             mats.append(shift_scale_rotate_matrix(self.size, self.size, angle, scale, dx, dy, flip))
             bcs.append([1 + self._u(-0.1, 0.1), self._u(-0.1, 0.1)] if self._u(0, 1) < 0.5 else [1.0, 0.0])
         return mats, bcs
+
+    def draw_elastic(self, n):
+        """-> (noise [n, 2, S, S] uniform in [-1, 1] on the device, alphas [n]: alpha for a sample chosen with probability p, else 0)"""
+        alpha, _, p = self.elastic
+        chosen = torch.rand(n, generator=self.elastic_gen) < p
+        s = self.size
+        noise = torch.rand(n, 2, s, s, device=self.device, generator=self.noise_gen) * 2 - 1
+        return noise, [alpha if c else 0.0 for c in chosen.tolist()]
 
     def _to_square(self, images, masks, n, hs, ws):
         """A.Resize(size, size) (trainer.py:85-87): aspect ratio not kept."""
@@ -85,15 +110,28 @@ class SegBatchTransform:
         img, msk = self._to_square(images, masks, n, hs, ws)
         bc = None
         if self.train:
-            mats, bcs = params if params is not None else self.draw(n)
+            mats, bcs = params[:2] if params is not None else self.draw(n)
+            el = params[2] if params is not None and len(params) > 2 else None      # (noise, alphas): a fixed elastic draw
             m1 = torch.tensor(mats, dtype=torch.float32, device=self.device)
             bc = torch.tensor(bcs, dtype=torch.float32, device=self.device)
+            if self.elastic is None:
+                if el is not None:
+                    raise ValueError("params carries an elastic draw, but the transform was built with elastic=None")
+                warp = lambda src, c, dst, nearest: lib.mi355_warp_u8(src, n, s, s, c, m1, dst, s, s, nearest, 1)  # noqa: E731
+            else:
+                noise, alphas = el if el is not None else self.draw_elastic(n)
+                noise = torch.as_tensor(noise, dtype=torch.float32, device=self.device)
+                if tuple(noise.shape) != (n, 2, s, s) or len(alphas) != n:
+                    raise ValueError(f"the elastic draw must be (noise [{n}, 2, {s}, {s}], {n} alphas)")
+                field = _elastic.elastic_field(noise, self.elastic[1])
+                al = torch.tensor(list(alphas), dtype=torch.float32, device=self.device)
+                warp = lambda src, c, dst, nearest: lib.mi355_warp_field_u8(src, n, s, s, c, m1, field, al, dst, s, s, nearest, 1)  # noqa: E731
             img2 = torch.empty_like(img)
-            lib.mi355_warp_u8(img, n, s, s, 3, m1, img2, s, s, 0, 1)
+            warp(img, 3, img2, 0)
             img = img2
             if msk is not None:
                 msk2 = torch.empty_like(msk)
-                lib.mi355_warp_u8(msk, n, s, s, 1, m1, msk2, s, s, 1, 1)
+                warp(msk, 1, msk2, 1)
                 msk = msk2
         x = torch.empty(n, 3, s, s, dtype=torch.float32, device=self.device)
         lib.mi355_normalize_u8(img, n, s, s, 3, bc, self.mean, self.std, x)

@@ -9,6 +9,7 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task seg --model attentionunet --epochs 2 --samples 64
     python utils/trainer.py --task seg --model r2attunet --seg-loss bce_dice --bce-weight 0.5 --dice-weight 0.5
     python utils/trainer.py --task seg --model attentionunet --seg-loss bce_dice --boundary-weight 0.01 --boundary-schedule rebalance
+    python utils/trainer.py --task seg --model attentionunet --data-root dataset --elastic-alpha 512 --elastic-sigma 20.5
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -77,7 +78,23 @@ def build_parser():
     ap.add_argument("--boundary-schedule", choices=["constant", "rebalance"], default="constant",
                     help="constant: region + w * boundary; rebalance: (1 - a) * region + a * boundary, a = min(w + epoch * step, 0.99)")
     ap.add_argument("--boundary-step", type=float, default=0.01, help="rebalance: growth of the boundary weight per epoch")
+    ap.add_argument("--elastic-alpha", type=float, default=0.0,
+                    help="--data-root: elastic deformation (A.ElasticTransform) in the train transforms, displacement scale in pixels; "
+                         "0 = off; the usual pairing is 2 * size with sigma 0.08 * size")
+    ap.add_argument("--elastic-sigma", type=float, default=None, help="elastic: Gaussian smoothing of the field in pixels; default 0.08 * size")
+    ap.add_argument("--elastic-p", type=float, default=0.5, help="elastic: probability per sample")
     return ap
+
+
+def elastic_arg(args):
+    """The ``elastic=`` argument of the train transforms: None with --elastic-alpha 0 (today's transforms), else (alpha, sigma, p),
+    validated here so that a bad flag fails before any data is read."""
+    if args.elastic_alpha < 0:
+        raise ValueError(f"--elastic-alpha must not be negative ({args.elastic_alpha})")
+    if args.elastic_alpha == 0:
+        return None
+    from utils.elastic import check_elastic
+    return check_elastic(args.elastic_alpha, 0.08 * args.size if args.elastic_sigma is None else args.elastic_sigma, args.elastic_p)
 
 
 def seg_criterion(args):
@@ -130,7 +147,7 @@ def main():
             from utils.dataset import ClassificationDataset, GpuBatchLoader, SegmentationDataset
             from utils.gpu_transforms import ClsBatchTransform, SegBatchTransform
             DS, TF = (ClassificationDataset, ClsBatchTransform) if task == "cls" else (SegmentationDataset, SegBatchTransform)
-            ds_tr = DS(args.data_root, TF(args.size, train=True, device=device), "train")
+            ds_tr = DS(args.data_root, TF(args.size, train=True, device=device, elastic=elastic_arg(args)), "train")
             ds_va = DS(args.data_root, TF(args.size, train=False, device=device), "train")
             if len(ds_tr) == 0:
                 say(f"{task} dataset is empty under {args.data_root}. Skipping.")
