@@ -11,7 +11,7 @@
 // mi355_conv2d_wgrad_reduce into the parameter-gradient layout.
 #include "common.hpp"
 #include "dma.hpp"
-#include "wgrad3x3_halo.hpp"
+#include "wgrad3x3_halo.hpp"      // (both: the row program of wgrad3x3_rows.hpp)
 #include "wgrad3x3_halo8.hpp"
 #include <stdlib.h>
 
@@ -231,19 +231,21 @@ static int halo_wgrad_mode(int N, int Ho, int Wo, int KH, int KW) {
   if (Wo == 16 && N % 2 == 0) return 2;
   return 0;
 }
+// what the modes are: waves of the kernel, pixels of an image row it takes at a time, and whether it takes two images at a time
+struct Wgrad3Mode { int waves, seg; bool paired; };
+static const Wgrad3Mode kWgrad3Mode[5] = {{0, 0, false}, {4, 32, false}, {4, 16, true}, {8, 64, false}, {8, 32, true}};
+// rows per work item
+static int halo_wgrad_rb(int Ho) { return Ho % 32 == 0 ? 32 : (Ho % 16 == 0 ? 16 : 8); }
 // work items of one (x, dy) pair: (image or image pair) x row segment x row band
-static int halo_wgrad_items(int mode, int N, int Ho, int Wo, int rb) {
-  switch (mode) {
-    case 1: return N * (Wo / 32) * (Ho / rb);
-    case 3: return N * (Wo / 64) * (Ho / rb);
-    default: return (N / 2) * (Ho / rb);             // 2, 4: image pairs
-  }
+static int halo_wgrad_items(int mode, int N, int Ho, int Wo) {
+  const Wgrad3Mode& m = kWgrad3Mode[mode];
+  return (m.paired ? N / 2 : N * (Wo / m.seg)) * (Ho / halo_wgrad_rb(Ho));
 }
 
 extern "C" int mi355_conv2d_wgrad_splits(int N, int Ho, int Wo, int Ci, int Co, int KH, int KW) {
   if (const int mode = halo_wgrad_mode(N, Ho, Wo, KH, KW)) {      // nine-tap kernel: 64x64 tiles, work items = 32-pixel-wide row bands
-    const int rb = Ho % 32 == 0 ? 32 : (Ho % 16 == 0 ? 16 : 8);
-    const long long items = halo_wgrad_items(mode, N, Ho, Wo, rb);
+    const bool eight = kWgrad3Mode[mode].waves == 8;
+    const long long items = halo_wgrad_items(mode, N, Ho, Wo);
     const long long tiles = (long long)ceil_div(Co, 64) * ceil_div(Ci, 64);
     // Four-wave kernel: ONE workgroup per CU.  Two are resident (254 VGPRs) and run the kernel 18 % faster on its own (3.4 vs 4.0 ms
     // per Attention U-Net step), but the kernel lives on the side stream next to the data-gradient chain: at one per CU it leaves
@@ -256,11 +258,11 @@ extern "C" int mi355_conv2d_wgrad_splits(int N, int Ho, int Wo, int Ci, int Co, 
     // partial slabs are written and reduced.  Step: 64 / 96 / 112 / 128 / 144 / 160 / 192 / 256 workgroups = 17.7 / 16.2 / 16.1 /
     // 15.40 / 15.6 / 15.65 / 15.9 / 16.3 ms against 15.74 for the four-wave kernel (profiles/r04a_wgs_sweep8.txt).
     static const int wgs_env = getenv("MI355_WGRAD_WGS") ? atoi(getenv("MI355_WGRAD_WGS")) : 0;      // (A/B switch)
-    int wgs = wgs_env > 0 ? wgs_env : (mode >= 3 ? 128 : 256);
+    int wgs = wgs_env > 0 ? wgs_env : (eight ? 128 : 256);
     // (A/B: another grid for the eight-wave kernel on images of at most MI355_WGRAD_DEEP_H rows)
     static const int deep_wgs = getenv("MI355_WGRAD_WGS_DEEP") ? atoi(getenv("MI355_WGRAD_WGS_DEEP")) : 0;
     static const int deep_h = getenv("MI355_WGRAD_DEEP_H") ? atoi(getenv("MI355_WGRAD_DEEP_H")) : 64;
-    if (mode >= 3 && deep_wgs > 0 && Ho <= deep_h) wgs = deep_wgs;
+    if (eight && deep_wgs > 0 && Ho <= deep_h) wgs = deep_wgs;
     long long s = wgs / tiles;
     if (s > items) s = items;
     const long long slab = (long long)Co * 9 * Ci * 4;
@@ -297,25 +299,14 @@ static int wgrad_launch(const WgradArgs& a, int splits, hipStream_t s) {
   return MI355_OK;
 }
 
-template <typename T, bool W16>
-static int launch_wgrad3x3(const Wgrad3Args& h, dim3 grid, hipStream_t s) {
-  constexpr int lds_bytes = Wgrad3Lds<W16>::BYTES;
-  static const hipError_t configured =
-      hipFuncSetAttribute((const void*)wgrad3x3_halo_kernel<T, W16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+// one launcher of the nine-tap kernels: the kernel, its waves and its LDS struct
+template <auto KERNEL, int WAVES, class LDS>
+static int launch_wgrad3_kernel(const Wgrad3Args& h, dim3 grid, hipStream_t s) {
+  constexpr int lds_bytes = LDS::BYTES;
+  static const hipError_t configured = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   if (configured != hipSuccess)
-    MI355_FAIL((int)configured, "wgrad3x3_halo: cannot reserve %d B of LDS: %s", lds_bytes, hipGetErrorString(configured));
-  hipLaunchKernelGGL((wgrad3x3_halo_kernel<T, W16>), grid, dim3(256), lds_bytes, s, h);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
-}
-template <typename T, bool W32>
-static int launch_wgrad3x3_8(const Wgrad3Args& h, dim3 grid, hipStream_t s) {
-  constexpr int lds_bytes = Wgrad8Lds::BYTES;
-  static const hipError_t configured =
-      hipFuncSetAttribute((const void*)wgrad3x3_halo8_kernel<T, W32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (configured != hipSuccess)
-    MI355_FAIL((int)configured, "wgrad3x3_halo8: cannot reserve %d B of LDS: %s", lds_bytes, hipGetErrorString(configured));
-  hipLaunchKernelGGL((wgrad3x3_halo8_kernel<T, W32>), grid, dim3(512), lds_bytes, s, h);
+    MI355_FAIL((int)configured, "wgrad3x3_halo%s: cannot reserve %d B of LDS: %s", WAVES == 8 ? "8" : "", lds_bytes, hipGetErrorString(configured));
+  hipLaunchKernelGGL(KERNEL, grid, dim3(64 * WAVES), lds_bytes, s, h);
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }
@@ -331,7 +322,7 @@ static int wgrad3_mode(int N, int Ho, int Wo, int KH, int KW, int stride, int pa
 // image goes to the generic kernel, which carries 64-bit addresses.  The queries are shape-level (they see neither the input extent
 // nor the channel strides) and do NOT apply this: a known gap, see DESIGN.md.
 static bool wgrad3_launchable(int hmode, int Hi, int Wi, int ldx, int Ho, int Wo, int ldy, int up, int esz) {
-  const long long img_lim = (1ll << 31) / (hmode == 2 || hmode == 4 ? 2 : 1);
+  const long long img_lim = (1ll << 31) / (kWgrad3Mode[hmode].paired ? 2 : 1);
   return Ho == (up ? 2 * Hi : Hi) && Wo == (up ? 2 * Wi : Wi) && (long long)Hi * Wi * ldx * esz < img_lim && (long long)Ho * Wo * ldy * esz < img_lim;
 }
 
@@ -342,23 +333,27 @@ static Wgrad3Args fill_wgrad3(const void* const* xs, const void* const* dys, int
   h.ws = ws;
   h.N = N; h.Hi = Hi; h.Wi = Wi; h.Ci = Ci; h.ldx = ldx;
   h.H = Ho; h.W = Wo; h.Co = Co; h.ldy = ldy; h.up = up ? 1 : 0;
-  h.RB = Ho % 32 == 0 ? 32 : (Ho % 16 == 0 ? 16 : 8);
-  h.items_per_app = halo_wgrad_items(hmode, N, Ho, Wo, h.RB);
+  h.RB = halo_wgrad_rb(Ho);
+  h.items_per_app = halo_wgrad_items(hmode, N, Ho, Wo);
   h.items = napp * h.items_per_app;
   h.items_per_block = ceil_div(h.items, splits);
   return h;
 }
 
 // launch and name of the nine-tap kernels, side by side (names as bench.py's per-kernel table books them)
-static const char* wgrad3_name(int hmode) { return hmode >= 3 ? "wgrad3x3_halo8_kernel" : "wgrad3x3_halo_kernel"; }
+static const char* wgrad3_name(int hmode) { return kWgrad3Mode[hmode].waves == 8 ? "wgrad3x3_halo8_kernel" : "wgrad3x3_halo_kernel"; }
 static int launch_wgrad3(const Wgrad3Args& h, int splits, int hmode, int dtype, hipStream_t s) {
   const dim3 grid(ceil_div(h.Co, 64) * ceil_div(h.Ci, 64), splits);
   const bool f16 = dtype == MI355_F16;
   switch (hmode) {
-    case 2: return f16 ? launch_wgrad3x3<f16_t, true>(h, grid, s) : launch_wgrad3x3<bf16_t, true>(h, grid, s);
-    case 3: return f16 ? launch_wgrad3x3_8<f16_t, false>(h, grid, s) : launch_wgrad3x3_8<bf16_t, false>(h, grid, s);
-    case 4: return f16 ? launch_wgrad3x3_8<f16_t, true>(h, grid, s) : launch_wgrad3x3_8<bf16_t, true>(h, grid, s);
-    default: return f16 ? launch_wgrad3x3<f16_t, false>(h, grid, s) : launch_wgrad3x3<bf16_t, false>(h, grid, s);
+    case 2: return f16 ? launch_wgrad3_kernel<wgrad3x3_halo_kernel<f16_t, true>, 4, Wgrad3Lds<true>>(h, grid, s)
+                       : launch_wgrad3_kernel<wgrad3x3_halo_kernel<bf16_t, true>, 4, Wgrad3Lds<true>>(h, grid, s);
+    case 3: return f16 ? launch_wgrad3_kernel<wgrad3x3_halo8_kernel<f16_t, false>, 8, Wgrad8Lds>(h, grid, s)
+                       : launch_wgrad3_kernel<wgrad3x3_halo8_kernel<bf16_t, false>, 8, Wgrad8Lds>(h, grid, s);
+    case 4: return f16 ? launch_wgrad3_kernel<wgrad3x3_halo8_kernel<f16_t, true>, 8, Wgrad8Lds>(h, grid, s)
+                       : launch_wgrad3_kernel<wgrad3x3_halo8_kernel<bf16_t, true>, 8, Wgrad8Lds>(h, grid, s);
+    default: return f16 ? launch_wgrad3_kernel<wgrad3x3_halo_kernel<f16_t, false>, 4, Wgrad3Lds<false>>(h, grid, s)
+                        : launch_wgrad3_kernel<wgrad3x3_halo_kernel<bf16_t, false>, 4, Wgrad3Lds<false>>(h, grid, s);
   }
 }
 

@@ -17,7 +17,13 @@ CASES = [  # N, Ci, H, W, Co, k, up          (halo 8x32 / 16x16 / ping-pong-elig
     (3, 256, 9, 7, 128, 1, 0), (4, 128, 24, 32, 64, 3, 0),
     # 128-channel ping-pong kernel at its default threshold (Ci >= 256): forward only / forward and data gradient / fused up-sampling
     (2, 256, 32, 64, 128, 3, 0), (2, 256, 16, 32, 256, 3, 0), (1, 256, 8, 16, 128, 3, 1),
+    # four-wave weight gradient on 32-pixel segments: odd batch with a 96-channel tail tile / three segments per row, one 8-row band
+    (3, 64, 16, 32, 96, 3, 0), (2, 64, 8, 96, 64, 3, 0),
 ]
+# N, C, H, W, extra input channels (ldx = Ci + extra): three distinct (x, dy) pairs in ONE mi355_conv2d_wgrad_multi launch
+# (16-pixel images in pairs / 64-pixel segments behind a foreign channel stride)
+MULTI_CASES = [(2, 64, 16, 16, 0), (2, 64, 16, 64, 32)]
+NAPP = 3
 
 
 # MI355_DUMP_SET=ws64: shapes of the weight-stationary kernel (Ci = 64 forward, Co = 64 data gradients), run by
@@ -93,6 +99,22 @@ def main():
                 ws = torch.empty(sp, co, k * k, ci, device=DEV)
                 lib.mi355_conv2d_wgrad(xd, dyd, ws, sp, n, h, w_, ci, ci, ho, wo, co, co, k, k, 1, p, up, code)
                 rec[f"{tag}_wgrad{rep}"] = ws.cpu().numpy()
+    for mi_, (n, c, h, w_, extra) in enumerate(MULTI_CASES):
+        for dtype in (torch.bfloat16, torch.float16):
+            g = torch.Generator().manual_seed(200 + mi_)
+            xs = [torch.zeros(n, h, w_, c + extra, dtype=dtype) for _ in range(NAPP)]
+            for xw in xs:
+                xw[..., extra:] = torch.randn(n, h, w_, c, generator=g).to(dtype)
+            xs = [xw.to(DEV) for xw in xs]
+            dys = [torch.randn(n, h, w_, c, generator=g).to(dtype).to(DEV) for _ in range(NAPP)]
+            ptrs = []
+            for i in range(6):
+                ptrs += [xs[i].data_ptr() + extra * 2, dys[i].data_ptr()] if i < NAPP else [None, None]
+            sp = lib.mi355_conv2d_wgrad_splits(n * NAPP, h, w_, c, c, 3, 3)
+            for rep in range(3):
+                ws = torch.empty(sp, c, 9, c, device=DEV)
+                lib.mi355_conv2d_wgrad_multi(*ptrs, NAPP, ws, sp, n, h, w_, c, c + extra, h, w_, c, c, 0, DTYPE_CODE[dtype])
+                rec[f"m{mi_}_{'bf16' if dtype == torch.bfloat16 else 'fp16'}_wgrad_multi{rep}"] = ws.cpu().numpy()
     torch.cuda.synchronize()
     np.savez(sys.argv[1], **rec)
 

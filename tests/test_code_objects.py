@@ -86,6 +86,14 @@ def test_eight_wave_weight_gradient_fits_two_waves_per_simd(kernels):
     assert len(_pick(kernels, r"wgrad3x3_halo8_kernel")) == 4          # bf16 / fp16 x (64-pixel segments, 32-pixel image pairs)
 
 
+def test_four_wave_weight_gradient_keeps_its_instantiations(kernels):
+    hit = _pick(kernels, r"wgrad3x3_halo_kernel")
+    for name, k in hit.items():
+        assert k["max_flat_workgroup_size"] == 256, (name, k)
+    assert len(hit) == 4                                               # bf16 / fp16 x (32-pixel segments, 16-pixel image pairs)
+    assert len(_pick(kernels, r"wgrad3x3_halo8?_kernel")) == 8
+
+
 STREAMING = (r"rowred_kernel|rowmap_kernel|bn_act_pool2_kernel|pack_im2col3_kernel|pack_weight_batched_kernel|pack_nchw_kernel|"
              r"gate_psi_fwd_kernel|gate_mul_bwd_kernel|wgrad_reduce_kernel")
 
