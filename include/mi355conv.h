@@ -449,6 +449,29 @@ int mi355_sepblur_reflect_f32(const float* src, int planes, int H, int W, const 
 int mi355_warp_field_u8(const uint8_t* src, int N, int Hs, int Ws, int C, const float* m, const float* field, const float* alpha,
                         uint8_t* dst, int H, int W, int nearest, int reflect, mi355_stream_t s);
 
+/* ---- CLAHE (contrast-limited adaptive histogram equalisation; A.CLAHE / cv2.createCLAHE — not in the reference's pipelines, an
+ * optional stage of ours).  The rules restate OpenCV's clahe.cpp; byte parity with cv2 itself has not been checked. --------------- */
+/* src: [N][H][W][C] uint8 interleaved, C = 1 or 3; every channel plane of every sample is equalised on its own.
+ * Padding: a plane with H % gy == 0 and W % gx == 0 is used as is; otherwise it is extended at the bottom by gy - H % gy rows AND on
+ * the right by gx - W % gx columns (a side that divides evenly still gets a full gy or gx: OpenCV's quirk), mirrored without
+ * repeating the edge pixel (BORDER_REFLECT_101: index i >= n reads 2 (n - 1) - i).  Tile th x tw = padded H / gy x padded W / gx,
+ * area = th tw.  MI355_ERR_ARG: a pad above H - 1 or W - 1, area > 2^24, a grid side outside 1 .. 64.
+ * Per tile, in integers: h = 256-bin histogram of the tile's pixels of the padded plane; with clip_count = lim > 0 (the caller's
+ * max(int(clip area / 256), 1), in double; 0 = no clipping): excess = sum max(h - lim, 0), h = min(h, lim), h += excess / 256, and
+ * with res = excess % 256 != 0 and step = max(256 / res, 1), bins 0, step, 2 step, ... get +1, stopping after res bins or at bin 255;
+ * luts[n][c][ty][tx][v] = sat_u8(rint(float(sum_{u <= v} h[u]) * (255.f / float(area)))): one fp32 multiply, rounded half to even.
+ * Integer LDS atomics and an integer scan: the order of the atomics cannot change a byte. */
+int mi355_clahe_lut_u8(const uint8_t* src, int N, int H, int W, int C, int gy, int gx, int clip_count /* lim, 0 = no clipping */,
+                       uint8_t* luts /* [N][C][gy][gx][256] */, mi355_stream_t s);
+/* dst[n][y][x][c] = the bilinear blend of the four neighbouring tiles' LUTs at v = src[n][y][x][c] (tile geometry as above; only
+ * the H x W pixels of the unpadded plane are written).  fp32, every operation rounded on its own, no FMA:
+ *   inv_tw = 1.f / tw; txf = x * inv_tw - 0.5f; tx1 = floor(txf); xa = txf - tx1; xa1 = 1.f - xa; then tx1 = max(tx1, 0),
+ *   tx2 = min(tx1 + 1, gx - 1) (tx1 + 1 taken before the clamp of tx1); the same in y;
+ *   dst = sat_u8(rint((L[ty1][tx1][v] * xa1 + L[ty1][tx2][v] * xa) * ya1 + (L[ty2][tx1][v] * xa1 + L[ty2][tx2][v] * xa) * ya)).
+ * luts: [N][C][gy][gx][256] as mi355_clahe_lut_u8 writes them (any bytes are accepted).  src and dst must differ. */
+int mi355_clahe_apply_u8(const uint8_t* src, int N, int H, int W, int C, int gy, int gx, const uint8_t* luts,
+                         uint8_t* dst, mi355_stream_t s);
+
 /* ---- PNG files -> uint8 batch on the host (utils/dataset.py:55,101-102: PIL Image.open(path).convert("RGB" | "L")) ----------- */
 /* Header fields of a PNG held in memory.  MI355_ERR_UNSUPPORTED (fields still filled) for an unknown interlace method or more
  * than 32768 pixels per side. */

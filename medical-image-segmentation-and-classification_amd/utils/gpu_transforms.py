@@ -12,7 +12,14 @@ the train transforms: per batch one uniform noise field drawn on the device, smo
 (utils/elastic.py, csrc/elastic.hip) and added, times ``alpha`` for the samples chosen with probability ``p`` and times 0 for the
 others, to the sampling coordinate of the ShiftScaleRotate warp: ``out(q) = src(M (q + alpha d(q)))``, one interpolation for both,
 the same field for image (bilinear) and mask (nearest).  Its draws come from generators of their own, so ``elastic=None`` leaves
-every launch and every draw of a given seed as it was."""
+every launch and every draw of a given seed as it was.
+
+``clahe=(clip, grid)`` adds ``A.CLAHE(clip_limit, tile_grid_size, p=1.0)`` (utils/clahe.py, csrc/clahe.hip; not in the reference's
+pipelines, off by default) to the S x S uint8 image right after ``A.Resize`` / ``A.PadIfNeeded`` and before the warp, in train AND in
+eval mode: it is deterministic preprocessing, not an augmentation, and a model trained with it must be validated, tested and served
+with the same values.  Every channel is equalised on its own (no LAB route); for the classifier the black padding is part of the
+histograms, as it is in Albumentations.  Masks are never touched and no random draw is consumed: ``clahe=None`` leaves every launch,
+every draw and every byte of a batch as it was."""
 from __future__ import annotations
 
 import math
@@ -20,6 +27,7 @@ import math
 import torch
 
 from mi355.lib import lib
+from utils import clahe as _clahe
 from utils import elastic as _elastic
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # trainer.py:48-49
@@ -47,9 +55,10 @@ class SegBatchTransform:
     """train_seg_transform / val_seg_transform (trainer.py:83-112) for a batch: ``(images uint8 [N,Hs,Ws,3], masks uint8
     [N,Hs,Ws]) -> (x float32 [N,3,S,S] normalised, y float32 [N,1,S,S] in {0,1})`` on the GPU.  ``params`` fixes the draws of a
     train-mode call: ``(mats, bcs)`` as ``draw`` returns them, plus, with ``elastic=(alpha, sigma, p)``, an optional third element
-    ``(noise [N,2,S,S], alphas [N])`` as ``draw_elastic`` returns it."""
+    ``(noise [N,2,S,S], alphas [N])`` as ``draw_elastic`` returns it.  ``clahe=(clip, grid)`` equalises the resized image (not the mask)
+    in both modes."""
 
-    def __init__(self, size=256, train=False, seed=0, device="cuda", elastic=None):
+    def __init__(self, size=256, train=False, seed=0, device="cuda", elastic=None, clahe=None):
         self.size, self.train, self.device = size, train, torch.device(device)
         self.gen = torch.Generator().manual_seed(seed)
         self.elastic = None
@@ -59,6 +68,12 @@ class SegBatchTransform:
             self.elastic = _elastic.check_elastic(*elastic)
             self.elastic_gen = torch.Generator().manual_seed(seed)                  # which samples: host; self.gen is not touched
             self.noise_gen = torch.Generator(device=self.device).manual_seed(seed)  # the noise field: drawn where it is used
+        self.clahe = None
+        if clahe is not None:
+            if len(clahe) != 2:
+                raise ValueError(f"clahe must be None or (clip, grid), got {clahe!r}")
+            self.clahe = _clahe.check_clahe(*clahe)
+            _clahe.tile_geometry(size, size, *self.clahe[1])
         self.mean = torch.tensor(IMAGENET_MEAN, device=self.device)
         self.std = torch.tensor(IMAGENET_STD, device=self.device)
 
@@ -108,6 +123,8 @@ class SegBatchTransform:
         assert images.dtype == torch.uint8 and c == 3
         s = self.size
         img, msk = self._to_square(images, masks, n, hs, ws)
+        if self.clahe is not None:
+            img = _clahe.clahe(img, *self.clahe)
         bc = None
         if self.train:
             mats, bcs = params[:2] if params is not None else self.draw(n)

@@ -11,7 +11,9 @@ padded to a multiple of ``bucket`` so that at most B / bucket launch plans ever 
 also the Grad-CAM map of every sample's predicted class, utils/explain.py).  ``process_images`` is ``process_image``'s
 per-file result — the red overlay at the file's own size (:399-413, mi355_overlay_mask) and the analysis text (:391-417) —
 for a list of PNG files, run as one batch.  ``postprocess`` (a utils.postprocess.MaskPostprocess; nothing in the reference) cleans
-the masks by connected components on the device before they are overlaid and adds the lesion count and area to the text."""
+the masks by connected components on the device before they are overlaid and adds the lesion count and area to the text.
+``pipeline.clahe = (clip, grid)`` equalises the resized images in ``process_files`` / ``process_images`` (utils/clahe.py) — the
+values the models were trained with (trainer.py --clahe-clip / --clahe-grid); the overlays are still drawn on the file's own pixels."""
 from __future__ import annotations
 
 import torch
@@ -28,8 +30,25 @@ class JointPipeline:
         self.keep = self.classes.index(positive)
         self.bucket = int(bucket)
         self.postprocess = postprocess
+        self._clahe = None
         self.classification_model = classification_model.to(self.device).eval()
         self.segmentation_model = None if segmentation_model is None else segmentation_model.to(self.device).eval()
+
+    @property
+    def clahe(self):
+        """None (default: the transforms as they were) or (clip, (gy, gx)): CLAHE on the resized images of ``process_files`` /
+        ``process_images``.  Set it to the (clip, grid) the models were trained with; validated on assignment."""
+        return self._clahe
+
+    @clahe.setter
+    def clahe(self, value):
+        if value is None:
+            self._clahe = None
+            return
+        from utils.clahe import check_clahe
+        if len(value) != 2:
+            raise ValueError(f"clahe must be None or (clip, grid), got {value!r}")
+        self._clahe = check_clahe(*value)
 
     @torch.no_grad()
     def predict(self, x, explain=False):
@@ -85,7 +104,7 @@ class JointPipeline:
         from utils.dataset import decode_batch, read_files
         from utils.gpu_transforms import SegBatchTransform
         imgs = decode_batch(read_files(paths), 3, threads, names=list(paths))
-        x = SegBatchTransform(size, train=False, device=self.device)(imgs.to(self.device, non_blocking=True))
+        x = SegBatchTransform(size, train=False, device=self.device, clahe=self.clahe)(imgs.to(self.device, non_blocking=True))
         return self.process_batch(x)
 
     def process_batch(self, x):
@@ -109,7 +128,7 @@ class JointPipeline:
         groups = {}
         for i, b in enumerate(bufs):
             groups.setdefault(png_size(b), []).append(i)
-        tf = SegBatchTransform(size, train=False, device=self.device)
+        tf = SegBatchTransform(size, train=False, device=self.device, clahe=self.clahe)
         order, imgs, xs = [], [], []
         for idx in groups.values():
             im = decode_batch([bufs[i] for i in idx], 3, threads, names=[paths[i] for i in idx]).to(self.device, non_blocking=True)

@@ -253,7 +253,7 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None, surface=False):
+                    seg_weights_dir=None, clahe=None, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -261,7 +261,8 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     its own loaders instead, and when neither exists the reference's "dataset not found" branch is taken (:637-639, :729-731).
     The CLIP / CLIPSeg entries (hub models, out of scope: SURVEY.md section 8) are reported and skipped.  Checkpoints are the
     reference's own format: a plain `state_dict` saved by `train` (helpers.py:394-400).  ``surface=True`` adds the surface-distance
-    metrics to every segmentation result (test_segmentation_model)."""
+    metrics to every segmentation result (test_segmentation_model).  ``clahe=(clip, grid)``: the default loaders' transforms equalise
+    the images (utils/clahe.py) — pass what the checkpoints were trained with (trainer.py --clahe-clip / --clahe-grid)."""
     from utils.helpers import get_class_model, get_seg_model
     if not torch.cuda.is_available():
         raise RuntimeError("test_all_models: the MI355X path needs a GPU (the reference falls back to the CPU, tester.py:524)")
@@ -301,9 +302,9 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             from utils.dataset import ClassificationDataset, GpuBatchLoader, SegmentationDataset
             from utils.gpu_transforms import ClsBatchTransform, SegBatchTransform
             if seg:
-                ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(IMG_SIZE, train=False, device=device), split="test")
+                ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(IMG_SIZE, train=False, device=device, clahe=clahe), split="test")
                 return GpuBatchLoader(ds, max(1, batch_size // 2), shuffle=False, device=device)
-            ds = ClassificationDataset(DATA_ROOT, ClsBatchTransform(IMG_SIZE, train=False, device=device), split="test")
+            ds = ClassificationDataset(DATA_ROOT, ClsBatchTransform(IMG_SIZE, train=False, device=device, clahe=clahe), split="test")
             return GpuBatchLoader(ds, batch_size, shuffle=False, device=device)
         except FileNotFoundError:
             return None
@@ -409,11 +410,20 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
     import argparse
     _ap = argparse.ArgumentParser(description="Test every checkpoint under weights/ on the test split")
     _ap.add_argument("--surface", action="store_true", help="also report Hausdorff, HD95, ASSD and surface Dice of the segmentation models")
+    _ap.add_argument("--clahe-clip", type=float, default=0.0,
+                     help="CLAHE clip limit the checkpoints were trained with (trainer.py --clahe-clip); 0 = off")
+    _ap.add_argument("--clahe-grid", type=int, default=8, help="CLAHE: tiles per side")
     _args = _ap.parse_args()
+    _kw = {}
+    if _args.clahe_clip != 0:
+        from utils.clahe import check_clahe
+        _kw["clahe"] = check_clahe(_args.clahe_clip, _args.clahe_grid)
     print("\n" + "=" * 80)
     print(" " * 20 + "MODEL TESTING UTILITY")
     print("=" * 80)
-    results = test_all_models(device="cuda", batch_size=16, surface=True) if _args.surface else test_all_models(device="cuda", batch_size=16)
+    if _args.surface:
+        _kw["surface"] = True
+    results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
     save_results_to_csv(results, cls_output_path="classification_test_results.csv", seg_output_path="segmentation_test_results.csv")
     print("\n[INFO] Testing complete!")

@@ -10,6 +10,7 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task seg --model r2attunet --seg-loss bce_dice --bce-weight 0.5 --dice-weight 0.5
     python utils/trainer.py --task seg --model attentionunet --seg-loss bce_dice --boundary-weight 0.01 --boundary-schedule rebalance
     python utils/trainer.py --task seg --model attentionunet --data-root dataset --elastic-alpha 512 --elastic-sigma 20.5
+    python utils/trainer.py --task seg --model attentionunet --data-root dataset --clahe-clip 4 --clahe-grid 8
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -83,6 +84,10 @@ def build_parser():
                          "0 = off; the usual pairing is 2 * size with sigma 0.08 * size")
     ap.add_argument("--elastic-sigma", type=float, default=None, help="elastic: Gaussian smoothing of the field in pixels; default 0.08 * size")
     ap.add_argument("--elastic-p", type=float, default=0.5, help="elastic: probability per sample")
+    ap.add_argument("--clahe-clip", type=float, default=0.0,
+                    help="--data-root: CLAHE (A.CLAHE) on the resized images of the train AND the validation transforms, clip limit; "
+                         "0 = off; test and serve the model with the same values (tester.py --clahe-clip, JointPipeline.clahe)")
+    ap.add_argument("--clahe-grid", type=int, default=8, help="CLAHE: tiles per side")
     return ap
 
 
@@ -95,6 +100,19 @@ def elastic_arg(args):
         return None
     from utils.elastic import check_elastic
     return check_elastic(args.elastic_alpha, 0.08 * args.size if args.elastic_sigma is None else args.elastic_sigma, args.elastic_p)
+
+
+def clahe_arg(args):
+    """The ``clahe=`` argument of the train and the validation transforms: None with --clahe-clip 0 (today's transforms), else
+    (clip, (grid, grid)), validated here so that a bad flag fails before any data is read."""
+    if not args.clahe_clip >= 0:
+        raise ValueError(f"--clahe-clip must not be negative ({args.clahe_clip})")
+    if args.clahe_clip == 0:
+        return None
+    from utils.clahe import check_clahe, tile_geometry
+    clip, grid = check_clahe(args.clahe_clip, args.clahe_grid)
+    tile_geometry(args.size, args.size, *grid)
+    return clip, grid
 
 
 def seg_criterion(args):
@@ -147,8 +165,8 @@ def main():
             from utils.dataset import ClassificationDataset, GpuBatchLoader, SegmentationDataset
             from utils.gpu_transforms import ClsBatchTransform, SegBatchTransform
             DS, TF = (ClassificationDataset, ClsBatchTransform) if task == "cls" else (SegmentationDataset, SegBatchTransform)
-            ds_tr = DS(args.data_root, TF(args.size, train=True, device=device, elastic=elastic_arg(args)), "train")
-            ds_va = DS(args.data_root, TF(args.size, train=False, device=device), "train")
+            ds_tr = DS(args.data_root, TF(args.size, train=True, device=device, elastic=elastic_arg(args), clahe=clahe_arg(args)), "train")
+            ds_va = DS(args.data_root, TF(args.size, train=False, device=device, clahe=clahe_arg(args)), "train")
             if len(ds_tr) == 0:
                 say(f"{task} dataset is empty under {args.data_root}. Skipping.")
                 continue
