@@ -394,6 +394,41 @@ int mi355_boundary_loss_fwd(const float* z, const int32_t* sd2, int B, long long
                             float* partial, float* loss, mi355_stream_t s);
 int mi355_boundary_loss_bwd(const float* z, const int32_t* sd2, int B, long long per, float weight, const float* gscale,
                             int accumulate, float* dz, mi355_stream_t s);
+/* Segmented stable argsort (nothing in the reference): keys [S][len] fp32 -> perm [S][len] int32, perm[s][k] = the index
+ * within segment s (0 .. len - 1) of its k-th smallest key.  The order is that of np.argsort(keys[s], kind="stable"):
+ * ascending as floats, -0.0 == +0.0 (canonicalised before the bit pattern is taken), equal keys in ascending index,
+ * -inf and +inf in their natural places.  NaN keys are unsupported as an order: the call still terminates, perm is
+ * still a permutation of every segment, nothing outside perm and ws is written.
+ *   mi355_segsort_tile:    keys one workgroup handles per pass; several workgroups share a segment longer than that.
+ *   mi355_segsort_ws_ints: int32 elements of scratch `ws` (-1 + last_error when the shape is out of range).
+ *   mi355_segsort_f32:     a least-significant-digit radix sort, four 8-bit passes of per-tile digit counts, a scan and
+ *     a scatter that is stable by construction (ballots, no returning atomic; integer LDS adds only for the counts).
+ *     Grid sizes depend on (S, len) alone; no allocation, no sync, no host read-back; bit-reproducible.  keys, ws and
+ *     perm must not overlap.
+ * 1 <= S <= 65535, len >= 1, S * len <= 2^26. */
+int mi355_segsort_tile(void);
+int mi355_segsort_ws_ints(int S, long long len);
+int mi355_segsort_f32(const float* keys, int S, long long len, int32_t* ws, long long ws_ints, int32_t* perm,
+                      mi355_stream_t s);
+/* Lovasz hinge (Berman, Triki, Blaschko, CVPR 2018, Algorithm 1; nothing in the reference): the convex surrogate of the
+ * Jaccard index, on fp32 logits z and targets t [S][len]; a segment is one image, or the whole batch with S = 1.
+ *   mi355_lovasz_ws_ints: int32 elements of scratch `ws` (-1 + last_error when the shape is out of range).
+ *   mi355_lovasz_fwd: y_i = t_i > thr, margin m_i = y_i ? z_i : -z_i, ranked ascending per segment by the sort above.
+ *     With P the segment's positives and c_k those among ranks 0 .. k: I_k = P - c_k, U_k = P + (k + 1) - c_k and
+ *     w_k = 1 / U_k (positive), I_k / ((U_k - 1) U_k) (negative, U_k > 1), 1 (negative, U_k = 1) — the Jaccard increment
+ *     in closed form from the integers.  L_s = sum_k max(1 - m_(k), 0) w_k;
+ *       loss[0] = (base ? base[0] : 0) + weight / S * sum_s L_s,
+ *       coef_i  = weight / S * (y_i ? -1 : +1) w_rank(i) where 1 - m_i > 0, else 0        (fp32 [S * len]).
+ *     Every term and fold in double, folds in a fixed order, coef and loss rounded to fp32 once; a NaN logit gives a NaN
+ *     loss.  `base` is a device scalar (the regional loss the term is added to) or NULL.  No floating-point atomics.
+ *   mi355_lovasz_bwd: dz_i (+)= gscale[0] * coef_i over n = S * len elements; gscale NULL = 1; accumulate != 0 adds the
+ *     rounded term to what dz holds, accumulate = 0 overwrites.  One pass, 16-byte accesses when coef and dz are 16-byte
+ *     aligned, the remainder element-wise.
+ * weight >= 0; shape limits as for the sort. */
+int mi355_lovasz_ws_ints(int S, long long len);
+int mi355_lovasz_fwd(const float* z, const float* t, int S, long long len, float thr, float weight, const float* base,
+                     int32_t* ws, long long ws_ints, float* coef, float* loss, mi355_stream_t s);
+int mi355_lovasz_bwd(const float* coef, long long n, const float* gscale, int accumulate, float* dz, mi355_stream_t s);
 
 /* ---- optimiser on flat fp32 buffers (utils/helpers.py:251,304,332-336) ---------------------- */
 /* sumsq partials of a flat gradient buffer; nblocks = mi355_rowreduce_blocks(n). */

@@ -262,6 +262,136 @@ class RegionBoundaryLoss(nn.Module):
                 f"max_weight={self.max_weight}")
 
 
+def _segmented_argsort(keys):
+    """mi355_segsort_f32 on a contiguous fp32 device tensor [S, len] -> int32 [S, len] (csrc/segsort.hip): per segment the order of
+    ``np.argsort(kind="stable")``.  No host round trip."""
+    S, n = keys.shape
+    need = lib.raw("mi355_segsort_ws_ints")(S, n)
+    if need <= 0:
+        raise RuntimeError(f"mi355_segsort_ws_ints failed: {lib.raw('mi355_last_error')().decode()}")
+    ws = torch.empty(need, dtype=torch.int32, device=keys.device)
+    perm = torch.empty(S, n, dtype=torch.int32, device=keys.device)
+    lib.mi355_segsort_f32(keys, S, n, ws, need, perm)
+    return perm
+
+
+def _lovasz_fwd(o, target, S, n, threshold, weight, base, loss):
+    """mi355_lovasz_fwd on contiguous fp32 device tensors of S * n elements -> the per-pixel coefficients (fp32 [S * n])."""
+    need = lib.raw("mi355_lovasz_ws_ints")(S, n)
+    if need <= 0:
+        raise RuntimeError(f"mi355_lovasz_ws_ints failed: {lib.raw('mi355_last_error')().decode()}")
+    ws = torch.empty(need, dtype=torch.int32, device=o.device)
+    coef = torch.empty(S * n, dtype=torch.float32, device=o.device)
+    lib.mi355_lovasz_fwd(o, target, S, n, float(threshold), float(weight), base, ws, need, coef, loss)
+    return coef
+
+
+class _RegionLovaszFn(torch.autograd.Function):
+    """region + Lovasz hinge as ONE autograd node, for the reason documented on _RegionBoundaryFn: every mi355 criterion's backward
+    returns the plan's ``dout`` buffer, so the regional backward writes ``dz`` and the Lovasz backward accumulates into it.
+    ``region`` = (bce_weight, dice_weight, smooth, per_sample) or None for the Lovasz term alone; next to a regional loss a Lovasz
+    weight of 0 launches nothing more than CombinedLoss does."""
+
+    @staticmethod
+    def forward(ctx, out, target, plan, region, lovasz_weight, per_image, threshold):
+        if out.dim() == 4 and out.shape[1] == 1:
+            B, per = out.shape[0], out.shape[2] * out.shape[3]
+        elif out.dim() == 3:
+            B, per = out.shape[0], out.shape[1] * out.shape[2]
+        else:
+            raise ValueError(f"the Lovasz hinge is defined for one-channel logits [B,1,H,W] or [B,H,W], got {tuple(out.shape)}")
+        if target.dtype != torch.float32 or not target.is_contiguous():
+            target = target.float().contiguous()
+        if target.numel() != out.numel():
+            raise ValueError(f"target size {tuple(target.shape)} must match input size {tuple(out.shape)}")
+        o = out.detach()
+        if not o.is_contiguous():
+            o = o.contiguous()
+        rows_r = 0
+        if region is not None:
+            rows_r = lib.mi355_seg_loss_rows(B, per)
+            if rows_r <= 0:
+                raise RuntimeError(f"mi355_seg_loss_rows failed: {lib.raw('mi355_last_error')().decode()}")
+        run_l = lovasz_weight > 0 or region is None
+        # one buffer: [rows_r x 4 regional partial sums | (a_b, c_b) per sample | regional loss, loss]
+        buf = torch.empty(rows_r * 4 + 2 * B + 2, dtype=torch.float32, device=out.device)
+        partial, state = buf[: rows_r * 4], buf[rows_r * 4: rows_r * 4 + 2 * B]
+        base, loss = buf[rows_r * 4 + 2 * B:][:1], buf[rows_r * 4 + 2 * B + 1:][:1]
+        if region is not None:
+            bw, dw, smooth, per_sample = region
+            lib.mi355_seg_loss_fwd(o, target, B, per, bw, dw, smooth, 1 if per_sample else 0, partial, state,
+                                   base if run_l else loss)
+        coef = None
+        if run_l:
+            S, n = (B, per) if per_image else (1, B * per)
+            coef = _lovasz_fwd(o, target, S, n, threshold, lovasz_weight, base if region is not None else None, loss)
+        ctx.o, ctx.t, ctx.plan, ctx.state, ctx.coef = o, target, plan, state, coef
+        ctx.region, ctx.run_l = region, run_l
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t, plan = ctx.o, ctx.t, ctx.plan
+        n = o.numel()
+        B = o.shape[0]
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        if ctx.region is not None:
+            lib.mi355_seg_loss_bwd(o, t, B, n // B, ctx.region[0], ctx.state, gs, dz)
+        if ctx.run_l:
+            lib.mi355_lovasz_bwd(ctx.coef, n, gs, 1 if ctx.region is not None else 0, dz)
+        return dz[:n].view(o.shape), None, None, None, None, None, None
+
+
+class LovaszHingeLoss(nn.Module):
+    """weight * Lovasz hinge (Berman, Triki, Blaschko, CVPR 2018, Algorithm 1): the convex surrogate of the Jaccard index of
+    ``target > threshold``, on a deterministic segmented sort of the margins (csrc/segsort.hip, csrc/lovasz.hip).  ``per_image=True``
+    evaluates it per image and averages the B terms (Berman's ``per_image``), ``per_image=False`` over the flattened batch.  Logits
+    [B,1,H,W] or [B,H,W], B * H * W <= 2^26.  To add it to a regional loss use RegionLovaszLoss: the sum of two mi355 criteria is not
+    a valid loss (both write their gradient into the plan's ``dout``)."""
+
+    def __init__(self, weight=1.0, per_image=True, threshold=0.5):
+        super().__init__()
+        if weight < 0:
+            raise ValueError(f"weight must not be negative ({weight})")
+        self.weight, self.per_image, self.threshold = float(weight), bool(per_image), float(threshold)
+
+    def forward(self, out, target):
+        if out.dtype != torch.float32:
+            out = out.float()
+        return _RegionLovaszFn.apply(out, target, getattr(out, "_mi355_plan", None), None, self.weight, self.per_image, self.threshold)
+
+    def extra_repr(self):
+        return f"weight={self.weight}, per_image={self.per_image}, threshold={self.threshold}"
+
+
+class RegionLovaszLoss(nn.Module):
+    """CombinedLoss(bce_weight, dice_weight, smooth, per_sample) + lovasz_weight * Lovasz hinge(per_image, threshold), as one
+    autograd node.  ``lovasz_weight=0`` is CombinedLoss bit for bit, with no further launch."""
+
+    def __init__(self, bce_weight=0.5, dice_weight=0.0, lovasz_weight=0.5, smooth=1.0, per_sample=False, per_image=True, threshold=0.5):
+        super().__init__()
+        if bce_weight < 0 or dice_weight < 0 or lovasz_weight < 0 or smooth < 0:
+            raise ValueError(f"bce_weight, dice_weight, lovasz_weight and smooth must not be negative "
+                             f"({bce_weight}, {dice_weight}, {lovasz_weight}, {smooth})")
+        self.bce_weight, self.dice_weight, self.lovasz_weight = float(bce_weight), float(dice_weight), float(lovasz_weight)
+        self.smooth, self.per_sample, self.per_image, self.threshold = float(smooth), bool(per_sample), bool(per_image), float(threshold)
+
+    def forward(self, out, target):
+        if out.dtype != torch.float32:
+            out = out.float()
+        region = (self.bce_weight, self.dice_weight, self.smooth, self.per_sample)
+        if self.bce_weight == 0 and self.dice_weight == 0 and self.lovasz_weight > 0:
+            region = None                      # the Lovasz term alone: what LovaszHingeLoss(lovasz_weight) launches, bit for bit
+        return _RegionLovaszFn.apply(out, target, getattr(out, "_mi355_plan", None), region, self.lovasz_weight, self.per_image,
+                                     self.threshold)
+
+    def extra_repr(self):
+        return (f"bce_weight={self.bce_weight}, dice_weight={self.dice_weight}, lovasz_weight={self.lovasz_weight}, "
+                f"smooth={self.smooth}, per_sample={self.per_sample}, per_image={self.per_image}, threshold={self.threshold}")
+
+
 class _CEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, out, target, smoothing, plan):

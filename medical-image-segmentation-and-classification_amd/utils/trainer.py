@@ -9,6 +9,7 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task seg --model attentionunet --epochs 2 --samples 64
     python utils/trainer.py --task seg --model r2attunet --seg-loss bce_dice --bce-weight 0.5 --dice-weight 0.5
     python utils/trainer.py --task seg --model attentionunet --seg-loss bce_dice --boundary-weight 0.01 --boundary-schedule rebalance
+    python utils/trainer.py --task seg --model attentionunet --seg-loss bce --lovasz-weight 0.5
     python utils/trainer.py --task seg --model attentionunet --data-root dataset --elastic-alpha 512 --elastic-sigma 20.5
     python utils/trainer.py --task seg --model attentionunet --data-root dataset --clahe-clip 4 --clahe-grid 8
 
@@ -68,9 +69,9 @@ def build_parser():
     ap.add_argument("--size", type=int, default=IMG_SIZE)
     ap.add_argument("--save-dir", default="weights")
     ap.add_argument("--data-root", default=None, help="dataset directory in the reference's layout; default: synthetic batches")
-    ap.add_argument("--seg-loss", choices=["bce", "dice", "bce_dice"], default="bce",
-                    help="segmentation loss: BCEWithLogits (the reference's train()), Dice, or bce_weight * BCE + dice_weight * Dice "
-                         "(the reference's DiceLoss / CombinedLoss, clip_seg_finetuner.py:40-74)")
+    ap.add_argument("--seg-loss", choices=["bce", "dice", "bce_dice", "lovasz"], default="bce",
+                    help="segmentation loss: BCEWithLogits (the reference's train()), Dice, bce_weight * BCE + dice_weight * Dice "
+                         "(the reference's DiceLoss / CombinedLoss, clip_seg_finetuner.py:40-74), or the Lovasz hinge (Berman et al. 2018)")
     ap.add_argument("--bce-weight", type=float, default=0.5, help="bce_dice: weight of the BCE term")
     ap.add_argument("--dice-weight", type=float, default=0.5, help="bce_dice: weight of the Dice term")
     ap.add_argument("--dice-per-sample", action="store_true", help="Dice term per image, averaged over the batch (default: over the whole batch)")
@@ -79,6 +80,10 @@ def build_parser():
     ap.add_argument("--boundary-schedule", choices=["constant", "rebalance"], default="constant",
                     help="constant: region + w * boundary; rebalance: (1 - a) * region + a * boundary, a = min(w + epoch * step, 0.99)")
     ap.add_argument("--boundary-step", type=float, default=0.01, help="rebalance: growth of the boundary weight per epoch")
+    ap.add_argument("--lovasz-weight", type=float, default=0.0,
+                    help="weight of the Lovasz hinge (Berman et al. 2018) added to --seg-loss bce|dice|bce_dice; 0 = off")
+    ap.add_argument("--lovasz-batch", action="store_true",
+                    help="Lovasz hinge over the flattened batch (default: per image, the B terms averaged)")
     ap.add_argument("--elastic-alpha", type=float, default=0.0,
                     help="--data-root: elastic deformation (A.ElasticTransform) in the train transforms, displacement scale in pixels; "
                          "0 = off; the usual pairing is 2 * size with sigma 0.08 * size")
@@ -117,9 +122,25 @@ def clahe_arg(args):
 
 def seg_criterion(args):
     """The loss module --seg-loss asks for; None = train()'s own default (BCEWithLogits).  With --boundary-weight > 0 it is that
-    regional loss plus the boundary loss, as one criterion (mi355.nn.RegionBoundaryLoss)."""
+    regional loss plus the boundary loss, as one criterion (mi355.nn.RegionBoundaryLoss); with --lovasz-weight > 0 that regional loss
+    plus the Lovasz hinge (mi355.nn.RegionLovaszLoss).  Three terms are not combined."""
     if args.boundary_weight < 0:
         raise ValueError(f"--boundary-weight must not be negative ({args.boundary_weight})")
+    if args.lovasz_weight < 0:
+        raise ValueError(f"--lovasz-weight must not be negative ({args.lovasz_weight})")
+    if args.lovasz_weight > 0 and args.boundary_weight > 0:
+        raise ValueError("--lovasz-weight and --boundary-weight cannot be combined: one term is added to --seg-loss at a time")
+    if args.lovasz_weight > 0 and args.seg_loss == "lovasz":
+        raise ValueError("--lovasz-weight adds the Lovasz hinge to --seg-loss bce|dice|bce_dice; --seg-loss lovasz is that loss alone")
+    if args.seg_loss == "lovasz":
+        if args.boundary_weight > 0:
+            raise ValueError("--boundary-weight is added to --seg-loss bce|dice|bce_dice, not to --seg-loss lovasz")
+        from mi355 import nn as mnn
+        return mnn.LovaszHingeLoss(per_image=not args.lovasz_batch)
+    if args.lovasz_weight > 0:
+        from mi355 import nn as mnn
+        bw, dw = {"bce": (1.0, 0.0), "dice": (0.0, 1.0), "bce_dice": (args.bce_weight, args.dice_weight)}[args.seg_loss]
+        return mnn.RegionLovaszLoss(bw, dw, args.lovasz_weight, per_sample=args.dice_per_sample, per_image=not args.lovasz_batch)
     if args.boundary_weight > 0:
         from mi355 import nn as mnn
         bw, dw = {"bce": (1.0, 0.0), "dice": (0.0, 1.0), "bce_dice": (args.bce_weight, args.dice_weight)}[args.seg_loss]
