@@ -9,35 +9,23 @@ last test asserts that every (launcher, dtype) pair and every branch of the two 
 
 The real-data chain at the end (reduce -> finalize -> apply on random operands) is held to bounds derived in the issue and
 checked on the CPU (tests/test_stream_exact_cpu.py); the test prints the measured err / bound per dtype and shape."""
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import time
-
 import pytest
 import torch
 
 import conv_bounds as cb
 import stream_exact as se
+from exact_harness import F32, BF, FP, DTYPES, G, SENT, NAN, Buf, Flat, Ledger, _run, _bits, _dn, _gen, _f, _fold  # noqa: F401
 from gpu_util import DEV, lib, DTYPE_CODE, _fma32
 
 pytestmark = pytest.mark.gpu
-F32, BF, FP = torch.float32, torch.bfloat16, torch.float16
-DTYPES = [F32, BF, FP]
-G = 8                 # guard channels on each side (16 / 32 bytes: the slices stay 16-byte aligned)
-SENT = 77.0
-NAN = float("nan")
 
 SWITCHES = {
     "wgs3": {"MI355_RR_WGS": "3", "MI355_RM_WGS": "3"},
     "rev": {"MI355_BN_APPLY_REV": "1", "MI355_RR_WGS": "3"},
     "nt": {"MI355_BN_REDUCE_NT": "1", "MI355_BN_APPLY_NT": "1"},
 }
-HERE = os.environ.get("MI355_STREAM_SWITCH", "")
-REPORT = os.environ.get("MI355_STREAM_REPORT", "")
-RESULTS = []          # rows dict(launcher, dtype, branches, n, switch)
+_LEDGER = Ledger("MI355_STREAM")
+HERE, RESULTS, _mark = _LEDGER.here, _LEDGER.results, _LEDGER.mark      # rows dict(launcher, dtype, branches, n, switch)
 CAP = 3 if HERE in ("wgs3", "rev") else 256            # grid cap of the fetch-batched reductions in this process
 CAP_MAP = 3 if HERE == "wgs3" else 1024                # ... and of the fetch-batched elementwise passes
 
@@ -45,116 +33,14 @@ CAP_MAP = 3 if HERE == "wgs3" else 1024                # ... and of the fetch-ba
 CH2 = [8, 40, 96, 64, 1024, 2048, 2560]
 
 
-def _dn(dtype):
-    return str(dtype).split(".")[-1]
-
-
 def _chans(dtype):
     return [c // 2 for c in CH2] if dtype == F32 else list(CH2)
-
-
-def _mark(launcher, dtype, *branches, n=1):
-    row = dict(launcher=launcher, dtype=_dn(dtype), branches=sorted(set(branches)), n=n, switch=HERE)
-    RESULTS.append(row)
-    if REPORT:
-        with open(REPORT, "a") as f:
-            f.write(json.dumps(row) + "\n")
-
-
-def _bits(t):
-    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-class Buf:
-    """[M + guard rows][G + C + G] of `dtype` on the device.  body given: an input (guards NaN; the launch must leave every byte
-    alone) or, with inout, an accumulated output (guards = sentinel); body None: an output (body NaN, guards = sentinel)."""
-
-    def __init__(self, M, C, dtype, gr, body=None, inout=False):
-        self.M, self.C, self.input = M, C, body is not None and not inout
-        w = torch.full((M + gr, C + 2 * G), NAN if self.input else SENT, dtype=dtype)
-        if body is None:
-            w[:M, G:G + C] = NAN
-        else:
-            se.assert_storable(body, dtype, "operand")
-            w[:M, G:G + C] = body.to(dtype)
-        self.init = w.to(DEV)
-        self.t = self.init.clone()
-        self.ptr = self.t.data_ptr() + G * self.t.element_size()
-        self.ld = C + 2 * G
-
-    def reset(self):
-        self.t.copy_(self.init)
-
-    def body(self):
-        return self.t[:self.M, G:G + self.C].cpu().double()
-
-    def guards_ok(self):
-        if self.input:
-            return torch.equal(_bits(self.t), _bits(self.init))
-        a = self.t.clone()
-        a[:self.M, G:G + self.C] = self.init[:self.M, G:G + self.C]
-        return torch.equal(_bits(a), _bits(self.init))
-
-
-class Flat(Buf):
-    """a contiguous fp32 output of n floats (partial rows, per-channel results) between two sentinel pads"""
-
-    def __init__(self, n, body=None):
-        self.M, self.C, self.input, self.n = 1, n, False, n
-        w = torch.full((n + 2 * G,), SENT, dtype=F32)
-        w[G:G + n] = NAN if body is None else body.float()
-        self.init = w.to(DEV)
-        self.t = self.init.clone()
-        self.ptr = self.t.data_ptr() + 4 * G
-
-    def body(self):
-        return self.t[G:G + self.n].cpu().double()
-
-    def guards_ok(self):
-        a = self.t.clone()
-        a[G:G + self.n] = self.init[G:G + self.n]
-        return torch.equal(_bits(a), _bits(self.init))
-
-
-def _run(what, fn, bufs, want, twice=True):
-    """launch; guards, NaN, bit-equality against want {Buf: fp64 reference of its body}; a second launch gives the same bytes"""
-    fn()
-    torch.cuda.synchronize()
-    for i, b in enumerate(bufs):
-        assert b.guards_ok(), f"{what}: guard rows / channels of buffer {i} changed"
-    first = {}
-    for b, ref in want.items():
-        got = b.body()
-        assert not torch.isnan(got).any(), f"{what}: {int(torch.isnan(got).sum())} elements never written (or NaN read)"
-        ref = ref.reshape(got.shape)
-        assert torch.equal(got, ref), f"{what}: {int((got != ref).sum())} of {got.numel()} elements differ, max |diff| {float((got - ref).abs().max())}"
-        first[b] = _bits(b.t).clone()
-    if twice:
-        for b in bufs:
-            b.reset()
-        fn()
-        torch.cuda.synchronize()
-        for b in want:
-            assert torch.equal(_bits(b.t), first[b]), f"{what}: a second launch gives other bytes"
-
-
-def _gen(*key):
-    return torch.Generator().manual_seed(sum(int(k) * (i + 3) for i, k in enumerate(key)) % (2 ** 31))
 
 
 def _edge_rows(rp, B, extra=()):
     """row counts without a whole batch and just around one, plus the case's extras"""
     ms = {1, rp - 1, rp * B - 1, rp * B, rp * B + 1} | set(extra)
     return sorted(m for m in ms if m >= 1)
-
-
-def _f(t):
-    return t.float().to(DEV)
-
-
-def _fold(partial, rows, nq, C):
-    """fp64 fold of the first `rows` partial rows: [nq, C]"""
-    return partial.reshape(-1, nq, C)[:rows].sum(0)
 
 
 def _fetch_branches(M, rp, B, grid):
@@ -784,28 +670,12 @@ def _children():
     return [pytest.param(k, id=k) for k in SWITCHES] if not HERE else []
 
 
-_CHILD_ROWS = []
-_CHILD_TIME = {}
+_CHILD_ROWS, _CHILD_TIME = _LEDGER.child_rows, _LEDGER.child_time
 
 
 @pytest.mark.parametrize("switch", _children())
 def test_switched_paths_in_a_child_process(switch):
-    fd, path = tempfile.mkstemp(suffix=".jsonl")
-    os.close(fd)
-    try:
-        env = dict(os.environ, MI355_STREAM_SWITCH=switch, MI355_STREAM_REPORT=path, **SWITCHES[switch])
-        t0 = time.time()
-        r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-s", "-m", "gpu", "-p", "no:cacheprovider"],
-                           env=env, capture_output=True, text=True, timeout=300)
-        _CHILD_TIME[switch] = time.time() - t0
-        print(r.stdout[-3000:])
-        assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
-        with open(path) as f:
-            rows = [json.loads(line) for line in f if line.strip()]
-        assert rows, f"child {switch} ran no case"
-        _CHILD_ROWS.extend(rows)
-    finally:
-        os.unlink(path)
+    _LEDGER.run_child(__file__, switch, SWITCHES[switch])
 
 
 def _coverage():
