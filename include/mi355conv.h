@@ -530,6 +530,35 @@ int mi355_gather_rows(const float* x, const int32_t* idx, int n, long long row, 
 int mi355_mask_scatter(const float* logit, const int32_t* idx, int n, long long per, float thr, uint8_t* out,
                        mi355_stream_t s);
 
+/* ---- test-time augmentation (utils/tta.py; nothing in the reference).  A view is (angle, scale, hflip) about the image centre; the
+ * host forms d2s (view pixel -> the source location it shows) and s2d (source pixel -> its place in the view), 2x3 row-major.  In
+ * all three kernels every fp32 operation is rounded on its own (no FMA), nothing is atomic and every sum runs in a fixed order:
+ * outputs are bit-identical run to run (tests/tta_ref.py restates them in numpy float32). -------------------------------------- */
+/* dst[n][c][y][x] (fp32 NCHW, like src) = bilinear sample of src[n][c] at sx = (m0 x + m1 y) + m2, sy = (m3 x + m4 y) + m5, x and y
+ * converted to float, m = m[n] ([N][6]): fx = floor(sx), ax = sx - fx, taps at fx, fx + 1 (likewise y) under reflect-101, and
+ * top = a00 (1 - ax) + a01 ax; bot = a10 (1 - ax) + a11 ax; out = top (1 - ay) + bot ay: mi355_warp_u8's reflect-mode sampling
+ * without the rounding to bytes.  src and dst must differ. */
+int mi355_warp_f32(const float* src, int N, int C, int H, int W, const float* m, float* dst, mi355_stream_t s);
+/* z: fp32 [K][N][H][W], the one-channel logit maps of K <= 16 views; s2d: [K][6].  For pixel q = (x, y) of sample n, in order
+ * k = 0 .. K - 1: p = s2d_k q (evaluated as above); view k is VALID at q iff 0 <= px <= W - 1 and 0 <= py <= H - 1; then v_k = the
+ * bilinear sample of z[k][n] at p (formula above; the taps fx + 1 / fy + 1 clamped to the map, where their weight is 0), and with
+ * prob != 0 v_k = sigmoid(v_k) (mi355_mask_scatter's expression).  Over the valid views, cnt of them:
+ *   mean[n][q] = (0 + v_k summed in order k) / (float)cnt;  var[n][q] = (sum in order k of (v_k - mean)^2) / (float)cnt (population)
+ *   votes[n][0][q] = #{valid k: v_k > thr (prob) or sigmoid(v_k) > thr (otherwise)}, votes[n][1][q] = cnt   (uint8 [N][2][H][W])
+ *   mask[idx ? idx[n] : n][q] = 255 where mean > thr (prob) or sigmoid(mean) > thr (otherwise), else 0  (mi355_mask_scatter's rule:
+ *   K = 1, the identity and prob = 0 give its bytes)
+ * var, votes, mask, idx may be NULL (skipped; idx: rows in place).  A pixel with no valid view gets 0 / 0: pass the identity as one
+ * view.  Known limit: within about 2 px of the border a valid view's taps may hold content the view got by reflection. */
+int mi355_tta_fold(const float* z, int K, int N, int H, int W, const float* s2d, int prob, float thr, const int32_t* idx, float* mean,
+                   float* var, uint8_t* votes, uint8_t* mask, mi355_stream_t s);
+/* logits: [K][B][C], K <= 16, B <= 1024.  softmax_k = mi355_cls_decide's: e_c = expf(z_c - max z), den = sum_c e_c in ascending c.
+ *   probs[b][c] = (0 + e_c / den summed in order k) / (float)K;  pred[b] = its first maximum;
+ *   conf[b] = (0 + (100 e_pred) / den summed in order k) / (float)K  (= 100 probs[b][pred] up to rounding; formed this way so that
+ *   K = 1 is mi355_cls_decide's 100 / den bit for bit);  agree[b] = #{k: first maximum of logits[k][b] == pred[b]};
+ * kept / n_kept as in mi355_cls_decide (same order, same padding contract). */
+int mi355_cls_tta_decide(const float* logits, int K, int B, int C, int keep_class, float* probs, int32_t* pred, float* conf,
+                         int32_t* agree, int32_t* kept, int32_t* n_kept, mi355_stream_t s);
+
 /* ---- Grad-CAM and image overlays (utils/explain.py; utils/pipeline.py process_images, reference pipeline.py:399-407) ---------- */
 /* dout[b][k] = (k == t_b) for the explained class t_b = target[b] when target is given (out of [0, K): a zero row, t_b = -1),
  * else the first maximum of logits[b][.]; target_out[b] = t_b (int32). */

@@ -2,6 +2,7 @@
 // VGG.py:103-122, helpers.py:124-143).  M = batch is tiny here, so these are latency-bound VALU
 // kernels; they exist so that the whole step runs on the library without torch math.
 #include "common.hpp"
+#include "decide.hpp"
 
 // one workgroup per (n, 64-channel group): 4 waves split the HW positions, lanes own channels
 template <typename T>
@@ -433,25 +434,14 @@ __global__ void cls_decide_kernel(const float* __restrict__ logits, int B, int C
   const int b = threadIdx.x;
   int mine = 0;
   if (b < B) {
-    const float* z = logits + (size_t)b * C;
-    float m = z[0];
-    int am = 0;
-    for (int c = 1; c < C; ++c)
-      if (z[c] > m) { m = z[c]; am = c; }          // first maximum (torch.max tie rule)
-    float den = 0.f;
-    for (int c = 0; c < C; ++c) den += expf(z[c] - m);
+    float m, den;
+    int am;
+    softmax_row_stats(logits + (size_t)b * C, C, m, am, den);
     pred[b] = am;
     conf[b] = 100.f / den;
     mine = am == keep_class;
   }
-  flag[b] = mine;
-  __syncthreads();
-  if (b == 0) {
-    int n = 0;
-    for (int i = 0; i < B; ++i)
-      if (flag[i]) kept[n++] = i;
-    n_kept[0] = n;
-  }
+  compact_kept(flag, b, B, mine, kept, n_kept);
 }
 
 extern "C" int mi355_cls_decide(const float* logits, int B, int C, int keep_class, int32_t* pred, float* conf, int32_t* kept,
@@ -485,7 +475,7 @@ __global__ void mask_scatter_kernel(const float* __restrict__ logit, const int32
   const float* src = logit + (size_t)blockIdx.y * per;
   uint8_t* dst = out + (size_t)idx[blockIdx.y] * per;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (long long)gridDim.x * blockDim.x)
-    dst[i] = 1.f / (1.f + expf(-src[i])) > thr ? 255 : 0;
+    dst[i] = sigmoid_f32(src[i]) > thr ? 255 : 0;
 }
 
 extern "C" int mi355_mask_scatter(const float* logit, const int32_t* idx, int n, long long per, float thr, uint8_t* out,

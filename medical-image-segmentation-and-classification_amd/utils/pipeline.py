@@ -13,7 +13,9 @@ per-file result — the red overlay at the file's own size (:399-413, mi355_over
 for a list of PNG files, run as one batch.  ``postprocess`` (a utils.postprocess.MaskPostprocess; nothing in the reference) cleans
 the masks by connected components on the device before they are overlaid and adds the lesion count and area to the text.
 ``pipeline.clahe = (clip, grid)`` equalises the resized images in ``process_files`` / ``process_images`` (utils/clahe.py) — the
-values the models were trained with (trainer.py --clahe-clip / --clahe-grid); the overlays are still drawn on the file's own pixels."""
+values the models were trained with (trainer.py --clahe-clip / --clahe-grid); the overlays are still drawn on the file's own pixels.
+``tta`` (a preset name or a list of views, utils/tta.py): both models predict on every view and the merged predictions decide; the
+result gains a per-pixel uncertainty map and the views' agreement, and the analysis text says how stable the highlighted area is."""
 from __future__ import annotations
 
 import torch
@@ -23,9 +25,21 @@ from mi355.lib import lib
 CLASSES = ["COVID", "Healthy", "Non-COVID"]          # pipeline.py:22
 
 
-class JointPipeline:
+class _KeywordOptions(type):
+    """``JointPipeline(..., tta=None, tta_merge="prob")``: the two options are keywords of the call, set through their properties once
+    ``__init__`` has run, so ``__init__`` keeps the positional parameter list its callers rely on."""
+
+    def __call__(cls, *args, tta=None, tta_merge="prob", **kwargs):
+        self = super().__call__(*args, **kwargs)
+        self.tta_merge = tta_merge
+        self.tta = tta
+        return self
+
+
+class JointPipeline(metaclass=_KeywordOptions):
     def __init__(self, classification_model, segmentation_model, device="cuda", classes=CLASSES, positive="COVID", bucket=4, postprocess=None):
         self.device = torch.device(device)
+        self._tta, self._tta_merge = None, "prob"
         self.classes = list(classes)
         self.keep = self.classes.index(positive)
         self.bucket = int(bucket)
@@ -50,6 +64,32 @@ class JointPipeline:
             raise ValueError(f"clahe must be None or (clip, grid), got {value!r}")
         self._clahe = check_clahe(*value)
 
+    @property
+    def tta(self):
+        """None (default: one forward pass per model) or the views of test-time augmentation (utils/tta.py): a preset name or a list
+        of (angle_deg, scale, hflip), validated on assignment and kept as that list."""
+        return self._tta
+
+    @tta.setter
+    def tta(self, value):
+        if value is None:
+            self._tta = None
+            return
+        from utils.tta import check_views
+        self._tta = check_views(value)
+
+    @property
+    def tta_merge(self):
+        """"prob" (default) or "logit": what the segmenter's views are averaged as"""
+        return self._tta_merge
+
+    @tta_merge.setter
+    def tta_merge(self, value):
+        from utils.tta import MERGES
+        if value not in MERGES:
+            raise ValueError(f"tta_merge must be one of {MERGES}, got {value!r}")
+        self._tta_merge = value
+
     @torch.no_grad()
     def predict(self, x, explain=False):
         """x: [B,3,H,W] normalised float (B <= 1024).  Returns a dict of device tensors:
@@ -58,9 +98,17 @@ class JointPipeline:
         the feature-map size), the Grad-CAM of each sample's predicted class; the logits then come from the classifier's explain
         plan, whose forward is the eval forward: every other output is the same, bit for bit.  With a ``postprocess``: ``masks`` are
         the cleaned masks, ``masks_raw`` the thresholded ones, ``n_lesions`` int32 [B] and ``area_percent`` float64 [B] the kept
-        components and their share of the image, ``lesions`` int32 [B,max_report,8] their rows (utils/postprocess.py)."""
+        components and their share of the image, ``lesions`` int32 [B,max_report,8] their rows (utils/postprocess.py).  With ``tta``:
+        ``pred`` / ``confidence`` come from the views' mean softmax and the masks from their merged maps (before any postprocess);
+        also ``agreement`` int32 [B] (views whose own class is ``pred``), ``uncertainty`` fp32 [B,H,W] (the variance of the views'
+        probabilities, or logits for tta_merge="logit"; zero where nothing was segmented) and ``stable_percent`` fp32 [B] (the share
+        of the pixels of ``masks`` — the cleaned masks with a postprocess — on which every view that sees them votes alike; 0 without a mask).  ``explain`` with ``tta``: ValueError."""
         x = x.to(self.device, dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
+        if self.tta is not None:
+            if explain:
+                raise ValueError("JointPipeline: explain=True is not defined with tta (Grad-CAM of an averaged prediction)")
+            return self._predict_tta(x)
         cams = None
         if explain:
             from utils.explain import GradCAM
@@ -95,6 +143,41 @@ class JointPipeline:
                        lesions=clean["out_c"])
         if cams is not None:
             out["cam"], out["cam_lowres"] = cams["cam"], cams["cam_lowres"]
+        return out
+
+    def _predict_tta(self, x):
+        """predict() with test-time augmentation: the same steps, every model call replaced by its K views and their merge"""
+        from utils.tta import TTAClassifier, fold_views, view_logits
+        B, _, H, W = x.shape
+        c = TTAClassifier(self.classification_model, self.tta, keep_class=self.keep, pad=self.bucket)(x)
+        pred, kept = c["pred"], c["kept"]
+        masks = torch.zeros(B, H, W, dtype=torch.uint8, device=self.device)
+        uncertainty = torch.zeros(B, H, W, dtype=torch.float32, device=self.device)
+        stable = torch.zeros(B, dtype=torch.float32, device=self.device)
+        segmented = pred == self.keep
+        same = None
+        n = int(c["n_kept"])                          # the one host sync: sizes the segmentation launches
+        if n and self.segmentation_model is not None:
+            npad = -(-n // self.bucket) * self.bucket
+            if npad > n:
+                kept[n:npad] = kept[0]                 # padding rows repeat a kept sample; their output is dropped
+            xs = torch.empty(npad, 3, H, W, dtype=torch.float32, device=self.device)
+            lib.mi355_gather_rows(x, kept, npad, 3 * H * W, xs)
+            f = fold_views(view_logits(self.segmentation_model, xs, self.tta, rows=n), self.tta, self.tta_merge, 0.5, kept, masks)
+            rows = kept[:n].long()
+            uncertainty[rows] = f["var"]
+            same = (f["votes"] == 0) | (f["votes"] == f["valid"])
+        elif self.segmentation_model is None:
+            segmented = torch.zeros_like(segmented)
+        out = {"pred": pred, "confidence": c["confidence"], "masks": masks, "segmented": segmented, "agreement": c["agreement"],
+               "uncertainty": uncertainty, "stable_percent": stable}
+        if self.postprocess is not None:
+            clean = self.postprocess(masks)
+            out.update(masks=clean["mask"], masks_raw=masks, n_lesions=clean["n_kept"], area_percent=clean["area_percent"],
+                       lesions=clean["out_c"])
+        if same is not None:                          # over the masks that are returned and overlaid: the cleaned ones with a postprocess
+            on = out["masks"][rows] != 0
+            stable[rows] = ((on & same).flatten(1).sum(1).float() / on.flatten(1).sum(1).clamp(min=1).float()) * 100
         return out
 
     def process_files(self, paths, size=256, threads=8):
@@ -138,6 +221,7 @@ class JointPipeline:
         r = self.predict(torch.cat(xs) if len(xs) > 1 else xs[0], explain=explain)
         pred, conf = r["pred"].cpu(), r["confidence"].cpu()
         lesions = (r["n_lesions"].cpu(), r["area_percent"].cpu()) if "n_lesions" in r else None
+        stable = r["stable_percent"].cpu() if "stable_percent" in r else None
         positive = self.classes[self.keep]
         results = [None] * len(paths)
         row = 0
@@ -159,6 +243,9 @@ class JointPipeline:
                     text += "\nInfection areas have been highlighted in red (segmentation model)."
                     if lesions is not None:
                         text += f"\nLesions: {int(lesions[0][row + j])} (area {float(lesions[1][row + j]):.2f}% of the image)."
+                    if stable is not None:
+                        text += (f"\nStable under test-time augmentation: {float(stable[row + j]):.2f}% of the highlighted pixels "
+                                 f"({len(self.tta)} views).")
                 else:
                     text += "\nWARNING: Segmentation model failed to load. Cannot highlight infection areas."
                 results[i] = (prediction, confidence, output_img, text) + ((heat[j],) if explain else ())

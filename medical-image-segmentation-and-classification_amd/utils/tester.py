@@ -178,18 +178,36 @@ def calculate_classification_metrics(all_preds, all_labels):
             "confusion_matrix": cm}
 
 
-def test_classification_model(model, test_loader, device, model_name):
+def test_classification_model(model, test_loader, device, model_name, tta=None):
+    """``tta`` (a preset name or a list of views, utils/tta.py; or pass ``utils.tta.TTAClassifier(model, views)`` as the model): the
+    predictions are the argmax of the views' mean softmax, and the result gains ``tta_agreement`` (%, the mean share of views whose
+    own argmax is the prediction) and ``tta_views``."""
+    from utils.tta import TTAClassifier
     model.eval()
-    preds, labels = [], []
+    preds, labels, agree = [], [], []
     print(f"\n{'=' * 60}\nTesting Classification Model: {model_name}\n{'=' * 60}")
+    if isinstance(model, TTAClassifier):
+        tta = cls_tta = model
+    elif tta is not None:
+        cls_tta = TTAClassifier(model, tta)
     with torch.no_grad():
         for images, y in test_loader:
-            out = model(images.to(device))
-            preds.append(torch.max(out, 1)[1])
+            if tta is None:
+                out = model(images.to(device))
+                preds.append(torch.max(out, 1)[1])
+            else:
+                r = cls_tta(images.to(device))
+                preds.append(r["pred"])
+                agree.append(r["agreement"])
             labels.append(y.to(device))
     m = calculate_classification_metrics(torch.cat(preds).cpu().numpy(), torch.cat(labels).cpu().numpy())
+    if tta is not None:
+        m["tta_views"] = len(cls_tta.views)
+        m["tta_agreement"] = float(torch.cat(agree).double().mean().cpu()) / m["tta_views"] * 100
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
     print(f"Accuracy:  {m['accuracy']:.2f}%\nPrecision: {m['precision']:.2f}%\nRecall:    {m['recall']:.2f}%\nF1 Score:  {m['f1']:.2f}%")
+    if tta is not None:
+        print(f"TTA agreement: {m['tta_agreement']:.2f}% of {m['tta_views']} views")
     print("\nPer-Class Metrics:")
     for i, c in enumerate(CLASSES[:len(m["f1_per_class"])]):   # (the reference indexes all of CLASSES, tester.py:282-296, and dies when a class is absent)
         print(f"\n{c}:\n  Precision: {m['precision_per_class'][i]:.2f}%\n  Recall:    {m['recall_per_class'][i]:.2f}%\n"
@@ -204,23 +222,39 @@ def test_classification_model(model, test_loader, device, model_name):
 
 def test_segmentation_model(model, test_loader, device, model_name, surface=False):
     """``surface=True`` adds hausdorff, hd95, assd (pixels; mean over the samples where both masks have a border), surface_dice
-    (%, tolerance 2 pixels) and surface_samples (how many samples entered those means) behind the six overlap metrics."""
+    (%, tolerance 2 pixels) and surface_samples (how many samples entered those means) behind the six overlap metrics.
+    Test-time augmentation: pass ``utils.tta.TTASegmenter(model, views, merge)`` as the model.  Every metric is then taken from the
+    views' merged map — the mean probability (``merge="prob"``) or the mean logit (``"logit"``) — and the result gains
+    ``tta_unanimous`` (%, the pixels on which every view that sees them votes alike; mean over the samples) and ``tta_views``."""
+    from utils.tta import TTASegmenter
     model.eval()
+    tta = seg_tta = model if isinstance(model, TTASegmenter) else None
+    is_logit = True                               # the model's output; with tta the merged map, a probability unless merge="logit"
+    if tta is not None:
+        tta_merge = seg_tta.merge
+        is_logit = tta_merge == "logit"
     tot = {k: 0.0 for k in ("iou", "dice", "pixel_accuracy", "precision", "recall", "f1")}
     n = 0
     print(f"\n{'=' * 60}\nTesting Segmentation Model: {model_name}\n{'=' * 60}")
-    pending = []
+    pending, unanimous = [], []
     with torch.no_grad():
         for images, masks in test_loader:
-            out = model(images.to(device))
+            if tta is None:
+                out = model(images.to(device))
+            else:
+                r = seg_tta(images.to(device))
+                out = r["mean"]
+                unanimous.append(((r["votes"] == 0) | (r["votes"] == r["valid"])).flatten(1).double().mean(1))
             if out.dim() == 3:
                 out = out.unsqueeze(1)
             masks = masks.to(device)
             B, per = out.shape[0], out[0].numel()
             cnt = torch.empty(B, 4, dtype=torch.float32, device=out.device)
-            lib.mi355_seg_counts(out.float().contiguous(), masks.float().contiguous(), cnt, B, per, 1, 0.5)
-            pending.append((cnt, per, _surface_raw(out, masks, True, 0.5, 95, 4) if surface else None))
+            lib.mi355_seg_counts(out.float().contiguous(), masks.float().contiguous(), cnt, B, per, 1 if is_logit else 0, 0.5)
+            pending.append((cnt, per, _surface_raw(out, masks, is_logit, 0.5, 95, 4) if surface else None))
     surf = []
+    if tta is not None:                           # read back with the counters below
+        unanimous = torch.cat(unanimous).cpu().numpy()
     for cnt, per, raw in pending:                 # single read-back after the loop
         for c in cnt.double().cpu().numpy():
             m = _metrics_from_counts(c, per)
@@ -236,11 +270,15 @@ def test_segmentation_model(model, test_loader, device, model_name, surface=Fals
         for k in SURFACE_KEYS:
             avg[k] = float(per_sample[k][ok].mean()) * (100.0 if k == "surface_dice" else 1.0) if ok.any() else float("nan")
         avg["surface_samples"] = int(ok.sum())
+    if tta is not None:
+        avg["tta_unanimous"] = float(unanimous.mean()) * 100
+        avg["tta_views"] = len(seg_tta.views)
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
     print(f"IoU (Jaccard):     {avg['iou']:.2f}%\nDice Coefficient:  {avg['dice']:.2f}%\nPixel Accuracy:    {avg['pixel_accuracy']:.2f}%")
     print(f"Precision:         {avg['precision']:.2f}%\nRecall:            {avg['recall']:.2f}%\nF1 Score:          {avg['f1']:.2f}%"
           + (f"\nHausdorff:         {avg['hausdorff']:.2f} px\nHD95:              {avg['hd95']:.2f} px\nASSD:              {avg['assd']:.2f} px\n"
              f"Surface Dice @2px: {avg['surface_dice']:.2f}% ({avg['surface_samples']} of {n} samples)" if surface else "")
+          + (f"\nTTA unanimous:     {avg['tta_unanimous']:.2f}% of the pixels ({avg['tta_views']} views, merged {tta_merge})" if tta is not None else "")
           + f"\n{'=' * 60}\n")
     return avg
 
@@ -253,7 +291,7 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None, clahe=None, surface=False):
+                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -262,8 +300,15 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     The CLIP / CLIPSeg entries (hub models, out of scope: SURVEY.md section 8) are reported and skipped.  Checkpoints are the
     reference's own format: a plain `state_dict` saved by `train` (helpers.py:394-400).  ``surface=True`` adds the surface-distance
     metrics to every segmentation result (test_segmentation_model).  ``clahe=(clip, grid)``: the default loaders' transforms equalise
-    the images (utils/clahe.py) — pass what the checkpoints were trained with (trainer.py --clahe-clip / --clahe-grid)."""
+    the images (utils/clahe.py) — pass what the checkpoints were trained with (trainer.py --clahe-clip / --clahe-grid).  ``tta`` /
+    ``tta_merge``: test-time augmentation for every model (test_classification_model(tta=...); the segmenters are handed to
+    test_segmentation_model wrapped in utils.tta.TTASegmenter)."""
     from utils.helpers import get_class_model, get_seg_model
+    if tta is not None:
+        from utils.tta import MERGES, check_views
+        tta = check_views(tta)
+        if tta_merge not in MERGES:
+            raise ValueError(f"tta_merge must be one of {MERGES}, got {tta_merge!r}")
     if not torch.cuda.is_available():
         raise RuntimeError("test_all_models: the MI355X path needs a GPU (the reference falls back to the CPU, tester.py:524)")
     device = torch.device(device)
@@ -317,7 +362,8 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         print(f"\n[WARNING] Classification test dataset not found: no loader given for {DATA_ROOT!r}")
         print("Skipping classification model testing...")
     else:
-        run(_CLS_FILES, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], test_classification_model, "Classification")
+        cls_test = (lambda m, l, d, name: test_classification_model(m, l, d, name, tta=tta)) if tta is not None else test_classification_model
+        run(_CLS_FILES, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], cls_test, "Classification")
     if seg_loader is None:
         print(f"\n[WARNING] Segmentation test dataset not found: no loader given for {DATA_ROOT!r}")
         print("Skipping segmentation model testing...")
@@ -325,6 +371,9 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         print("\n[WARNING] Segmentation test dataset is empty. Skipping segmentation testing.")
     else:
         seg_test = (lambda m, l, d, name: test_segmentation_model(m, l, d, name, surface=True)) if surface else test_segmentation_model
+        if tta is not None:
+            from utils.tta import TTASegmenter
+            seg_test = lambda m, l, d, name: test_segmentation_model(TTASegmenter(m, tta, tta_merge), l, d, name, surface=surface)  # noqa: E731
         run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
     return results
 
@@ -413,6 +462,9 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
     _ap.add_argument("--clahe-clip", type=float, default=0.0,
                      help="CLAHE clip limit the checkpoints were trained with (trainer.py --clahe-clip); 0 = off")
     _ap.add_argument("--clahe-grid", type=int, default=8, help="CLAHE: tiles per side")
+    _ap.add_argument("--tta", choices=("hflip", "rot", "full"), default=None,
+                     help="test-time augmentation: predict on these views and score the merged prediction (utils/tta.py)")
+    _ap.add_argument("--tta-merge", choices=("prob", "logit"), default="prob", help="TTA: average the probabilities or the logits")
     _args = _ap.parse_args()
     _kw = {}
     if _args.clahe_clip != 0:
@@ -423,6 +475,8 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
     print("=" * 80)
     if _args.surface:
         _kw["surface"] = True
+    if _args.tta is not None:
+        _kw.update(tta=_args.tta, tta_merge=_args.tta_merge)
     results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
     save_results_to_csv(results, cls_output_path="classification_test_results.csv", seg_output_path="segmentation_test_results.csv")
