@@ -429,6 +429,40 @@ int mi355_lovasz_ws_ints(int S, long long len);
 int mi355_lovasz_fwd(const float* z, const float* t, int S, long long len, float thr, float weight, const float* base,
                      int32_t* ws, long long ws_ints, float* coef, float* loss, mi355_stream_t s);
 int mi355_lovasz_bwd(const float* coef, long long n, const float* gscale, int accumulate, float* dz, mi355_stream_t s);
+/* Threshold-free evaluation (nothing in the reference): ROC-AUC, average precision, the ROC / precision-recall operating
+ * points and the calibration of a classifier.
+ *   mi355_rank_ws_ints: int32 elements of scratch `ws` (-1 + last_error when the shape is out of range).
+ *   mi355_rank_metrics: fp32 scores [S][len], ranked ascending per segment by the sort above.  The positives come from
+ *     exactly one of `target` (fp32 [S][len], y = target > thr) and `labels` (int32 [len], shared by the segments,
+ *     y = (labels[i] == s): one-vs-rest without a one-hot array; thr is ignored); the other is NULL.  A tie group g is a
+ *     run of equal scores (-0.0 == +0.0); A_g, B_g = the negatives, positives up to and including group g, A_0 = B_0 = 0.
+ *       counts int64 [S][4] = P, N, U2 = sum_g (B_g - B_{g-1}) (A_g + A_{g-1}), T
+ *         U2 is twice the Mann-Whitney statistic with ties counted half, an exact integer (<= 2^51); T the number of
+ *         distinct scores.  AUROC = U2 / (2 P N) is the caller's, NaN when P = 0 or N = 0.
+ *       ap double [S] = sum_g (p_g / P) tp_g / (tp_g + fp_g), p_g = B_g - B_{g-1}, tp_g = P - B_{g-1}, fp_g = N - A_{g-1}:
+ *         the step-wise average precision; NaN when P = 0.  Double partials per tile, folded in a fixed order.
+ *       thresholds fp32 [S][len], tp, fp int32 [S][len], npoints int32 [S]: the T operating points (score_g, tp_g, fp_g) in
+ *         DESCENDING threshold order; only the first npoints[s] = T entries of a row are written.  All four NULL: skipped.
+ *     No floating-point atomics, no allocation, no sync, no host read-back; bit-reproducible.  NaN scores are not an
+ *     order: that segment's outputs are unspecified, every write stays in bounds and P + N == len.
+ *   mi355_cls_calibration_ws_ints: int32 elements of scratch `ws` (-1 + last_error when an argument is out of range).
+ *   mi355_cls_calibration: x fp32 [N][C] logits (is_prob = 0) or probabilities (is_prob != 0), labels int32 [N].  The
+ *     softmax is evaluated in double after subtracting the row maximum; conf = the largest probability, pred = the first
+ *     argmax, bin = min(bins - 1, max(0, ceil(conf * bins) - 1)) — the bins (k / M, (k + 1) / M] of Guo et al. 2017.
+ *       bin_count, bin_correct int64 [bins]; bin_conf double [bins] = the sum of the confidences, folded in a fixed order
+ *       out double [3] = mean NLL (logits: log sum_j exp(x_j - max) - (x_y - max)), mean multi-class Brier score
+ *         sum_j (p_j - 1[j = y])^2, ECE = sum_m |bin_correct_m - bin_conf_m| / N
+ *       scores_t fp32 [C][N] = the probabilities rounded to fp32 once, transposed: one segment per class for
+ *         mi355_rank_metrics(labels).
+ * Shape limits of mi355_rank_metrics as for the sort; N >= 1, 1 <= C <= 4096, N * C <= 2^26, 1 <= bins <= 1024. */
+int mi355_rank_ws_ints(int S, long long len);
+int mi355_rank_metrics(const float* scores, const float* target, const int32_t* labels, int S, long long len, float thr,
+                       int32_t* ws, long long ws_ints, int64_t* counts, double* ap, float* thresholds, int32_t* tp,
+                       int32_t* fp, int32_t* npoints, mi355_stream_t s);
+int mi355_cls_calibration_ws_ints(int N, int C, int bins);
+int mi355_cls_calibration(const float* x, int N, int C, int is_prob, const int32_t* labels, int bins, int32_t* ws,
+                          long long ws_ints, int64_t* bin_count, int64_t* bin_correct, double* bin_conf, double* out,
+                          float* scores_t, mi355_stream_t s);
 
 /* ---- optimiser on flat fp32 buffers (utils/helpers.py:251,304,332-336) ---------------------- */
 /* sumsq partials of a flat gradient buffer; nblocks = mi355_rowreduce_blocks(n). */

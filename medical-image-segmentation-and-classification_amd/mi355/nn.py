@@ -286,6 +286,44 @@ def _lovasz_fwd(o, target, S, n, threshold, weight, base, loss):
     return coef
 
 
+def _rank_metrics(scores, target, labels, threshold, curve=False):
+    """mi355_rank_metrics on a contiguous fp32 device tensor [S, len] with ``target`` (fp32 [S, len]) or ``labels`` (int32 [len]) ->
+    (counts int64 [S, 4], ap float64 [S], None or (thresholds fp32 [S, len], tp int32 [S, len], fp int32 [S, len], npoints int32 [S]))
+    (csrc/ranking.hip).  The curve rows are written up to npoints[s] only.  No host round trip."""
+    S, n = scores.shape
+    need = lib.raw("mi355_rank_ws_ints")(S, n)
+    if need <= 0:
+        raise RuntimeError(f"mi355_rank_ws_ints failed: {lib.raw('mi355_last_error')().decode()}")
+    dev = scores.device
+    ws = torch.empty(need, dtype=torch.int32, device=dev)
+    counts = torch.empty(S, 4, dtype=torch.int64, device=dev)
+    ap = torch.empty(S, dtype=torch.float64, device=dev)
+    pts = None
+    if curve:
+        pts = (torch.empty(S, n, dtype=torch.float32, device=dev), torch.empty(S, n, dtype=torch.int32, device=dev),
+               torch.empty(S, n, dtype=torch.int32, device=dev), torch.empty(S, dtype=torch.int32, device=dev))
+    lib.mi355_rank_metrics(scores, target, labels, S, n, float(threshold), ws, need, counts, ap, *(pts or (None,) * 4))
+    return counts, ap, pts
+
+
+def _cls_calibration(x, labels, bins, is_prob):
+    """mi355_cls_calibration on a contiguous fp32 device tensor [N, C] and int32 labels [N] -> (bin_count int64 [bins], bin_correct
+    int64 [bins], bin_conf float64 [bins], out float64 [3] = NLL, Brier, ECE, scores_t fp32 [C, N]).  No host round trip."""
+    N, C = x.shape
+    need = lib.raw("mi355_cls_calibration_ws_ints")(N, C, bins)
+    if need <= 0:
+        raise RuntimeError(f"mi355_cls_calibration_ws_ints failed: {lib.raw('mi355_last_error')().decode()}")
+    dev = x.device
+    ws = torch.empty(need, dtype=torch.int32, device=dev)
+    bin_count = torch.empty(bins, dtype=torch.int64, device=dev)
+    bin_correct = torch.empty(bins, dtype=torch.int64, device=dev)
+    bin_conf = torch.empty(bins, dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    scores_t = torch.empty(C, N, dtype=torch.float32, device=dev)
+    lib.mi355_cls_calibration(x, N, C, 1 if is_prob else 0, labels, bins, ws, need, bin_count, bin_correct, bin_conf, out, scores_t)
+    return bin_count, bin_correct, bin_conf, out, scores_t
+
+
 class _RegionLovaszFn(torch.autograd.Function):
     """region + Lovasz hinge as ONE autograd node, for the reason documented on _RegionBoundaryFn: every mi355 criterion's backward
     returns the plan's ``dout`` buffer, so the regional backward writes ``dz`` and the Lovasz backward accumulates into it.

@@ -3,7 +3,9 @@ reference's utils/tester.py (segmentation metrics :92-193, classification metric
 loops :197-312).  Per-sample counters come from one HIP reduction per batch instead of ~9 host
 syncs per sample.  On request (``surface=True`` / ``--surface``) the segmentation loop also reports
 the boundary metrics the reference lacks: Hausdorff distance, HD95, ASSD and surface Dice
-(csrc/surface.hip; DESIGN.md, "Surface-distance metrics")."""
+(csrc/surface.hip; DESIGN.md, "Surface-distance metrics"), and (``auc=True`` / ``--auc``) both loops report the threshold-free figures:
+ROC-AUC and average precision — per class for the classifiers, per image over the pixels for the segmenters
+(``evaluate_segmentation_model``) — and the classifiers' calibration (ECE, Brier score, NLL), from csrc/ranking.hip ("Ranking metrics and calibration")."""
 import math
 import os
 
@@ -178,13 +180,25 @@ def calculate_classification_metrics(all_preds, all_labels):
             "confusion_matrix": cm}
 
 
-def test_classification_model(model, test_loader, device, model_name, tta=None):
+def _nanmean(values):
+    """-> (mean of the values that are not NaN, or NaN; how many entered it)"""
+    v = np.asarray(values, dtype=np.float64)
+    ok = ~np.isnan(v)
+    return (float(v[ok].mean()) if ok.any() else float("nan")), int(ok.sum())
+
+
+def test_classification_model(model, test_loader, device, model_name, tta=None, auc=False, calibration_bins=15):
     """``tta`` (a preset name or a list of views, utils/tta.py; or pass ``utils.tta.TTAClassifier(model, views)`` as the model): the
     predictions are the argmax of the views' mean softmax, and the result gains ``tta_agreement`` (%, the mean share of views whose
-    own argmax is the prediction) and ``tta_views``."""
+    own argmax is the prediction) and ``tta_views``.
+    ``auc=True``: the logits (with ``tta`` the views' mean softmax) stay on the device across the loop; one calibration call and one
+    ranking call after it (utils/ranking.py, one segment per class, one-vs-rest) add ``auroc`` and ``average_precision`` (fractions in
+    [0, 1]: the macro mean over the classes where they are defined — a class with no sample, or for auroc with every sample, is left
+    out), ``auc_classes`` (how many classes entered the auroc mean), ``auroc_per_class``, ``ap_per_class`` and the calibration figures
+    ``ece`` (over ``calibration_bins`` confidence bins), ``brier`` and ``nll``."""
     from utils.tta import TTAClassifier
     model.eval()
-    preds, labels, agree = [], [], []
+    preds, labels, agree, kept_scores = [], [], [], []
     print(f"\n{'=' * 60}\nTesting Classification Model: {model_name}\n{'=' * 60}")
     if isinstance(model, TTAClassifier):
         tta = cls_tta = model
@@ -195,23 +209,42 @@ def test_classification_model(model, test_loader, device, model_name, tta=None):
             if tta is None:
                 out = model(images.to(device))
                 preds.append(torch.max(out, 1)[1])
+                if auc:
+                    kept_scores.append(out.float())
             else:
                 r = cls_tta(images.to(device))
                 preds.append(r["pred"])
                 agree.append(r["agreement"])
+                if auc:
+                    kept_scores.append(r["probs"].float())
             labels.append(y.to(device))
     m = calculate_classification_metrics(torch.cat(preds).cpu().numpy(), torch.cat(labels).cpu().numpy())
     if tta is not None:
         m["tta_views"] = len(cls_tta.views)
         m["tta_agreement"] = float(torch.cat(agree).double().mean().cpu()) / m["tta_views"] * 100
+    if auc:
+        from utils.ranking import calibration, rank_metrics
+        y = torch.cat(labels).to(torch.int32)
+        cal = calibration(torch.cat(kept_scores), y, bins=calibration_bins, is_prob=tta is not None)
+        rk = rank_metrics(cal["scores_t"], labels=y)
+        m["auroc_per_class"] = rk["auroc"].cpu().numpy()
+        m["ap_per_class"] = rk["average_precision"].cpu().numpy()
+        m["auroc"], m["auc_classes"] = _nanmean(m["auroc_per_class"])
+        m["average_precision"] = _nanmean(m["ap_per_class"])[0]
+        m["ece"], m["brier"], m["nll"] = float(cal["ece"].cpu()), float(cal["brier"].cpu()), float(cal["nll"].cpu())
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
     print(f"Accuracy:  {m['accuracy']:.2f}%\nPrecision: {m['precision']:.2f}%\nRecall:    {m['recall']:.2f}%\nF1 Score:  {m['f1']:.2f}%")
     if tta is not None:
         print(f"TTA agreement: {m['tta_agreement']:.2f}% of {m['tta_views']} views")
+    if auc:
+        print(f"AUROC / AP: {m['auroc']:.4f} / {m['average_precision']:.4f} (macro, one-vs-rest, {m['auc_classes']} classes)")
+        print(f"ECE ({calibration_bins} bins) / Brier / NLL: {m['ece']:.4f} / {m['brier']:.4f} / {m['nll']:.4f}")
     print("\nPer-Class Metrics:")
     for i, c in enumerate(CLASSES[:len(m["f1_per_class"])]):   # (the reference indexes all of CLASSES, tester.py:282-296, and dies when a class is absent)
         print(f"\n{c}:\n  Precision: {m['precision_per_class'][i]:.2f}%\n  Recall:    {m['recall_per_class'][i]:.2f}%\n"
-              f"  F1 Score:  {m['f1_per_class'][i]:.2f}%")
+              f"  F1 Score:  {m['f1_per_class'][i]:.2f}%"
+              + (f"\n  AUROC:     {m['auroc_per_class'][i]:.4f}\n  AP:        {m['ap_per_class'][i]:.4f}"
+                 if auc and i < len(m["auroc_per_class"]) else ""))
     print("\nConfusion Matrix:")
     print((" " * 25).join(f"{c:>12}" for c in CLASSES))      # the reference's header: names joined by 12 + 1 + 12 blanks (:299)
     for i, row in enumerate(m["confusion_matrix"][:len(CLASSES)]):
@@ -221,11 +254,23 @@ def test_classification_model(model, test_loader, device, model_name, tta=None):
 
 
 def test_segmentation_model(model, test_loader, device, model_name, surface=False):
+    """The segmentation eval loop with the reference's arguments (plus ``surface``): evaluate_segmentation_model without the ranking
+    figures, which documents both."""
+    return evaluate_segmentation_model(model, test_loader, device, model_name, surface=surface)
+
+
+def evaluate_segmentation_model(model, test_loader, device, model_name, surface=False, auc=False):
     """``surface=True`` adds hausdorff, hd95, assd (pixels; mean over the samples where both masks have a border), surface_dice
     (%, tolerance 2 pixels) and surface_samples (how many samples entered those means) behind the six overlap metrics.
     Test-time augmentation: pass ``utils.tta.TTASegmenter(model, views, merge)`` as the model.  Every metric is then taken from the
     views' merged map — the mean probability (``merge="prob"``) or the mean logit (``"logit"``) — and the result gains
-    ``tta_unanimous`` (%, the pixels on which every view that sees them votes alike; mean over the samples) and ``tta_views``."""
+    ``tta_unanimous`` (%, the pixels on which every view that sees them votes alike; mean over the samples) and ``tta_views``.
+    ``auc=True`` (this function only: test_segmentation_model keeps the argument list its callers know) adds ``pixel_auroc`` and
+    ``pixel_ap`` (fractions in [0, 1]): ROC-AUC and average precision of each image's pixel scores against ``masks > 0.5``, one ranking call per batch (utils/ranking.py), averaged over the samples where they are defined —
+    ``auc_samples`` of them: an image without a positive pixel (or without a negative one) has no ROC-AUC and is counted out.  The LOGITS
+    are ranked: the sigmoid is monotone, so the order, the ties that matter and with them every figure are those of the probabilities
+    in exact arithmetic, and nothing passes through expf.  With test-time augmentation the merged map is ranked — with
+    ``merge="prob"`` the merged probabilities."""
     from utils.tta import TTASegmenter
     model.eval()
     tta = seg_tta = model if isinstance(model, TTASegmenter) else None
@@ -236,7 +281,9 @@ def test_segmentation_model(model, test_loader, device, model_name, surface=Fals
     tot = {k: 0.0 for k in ("iou", "dice", "pixel_accuracy", "precision", "recall", "f1")}
     n = 0
     print(f"\n{'=' * 60}\nTesting Segmentation Model: {model_name}\n{'=' * 60}")
-    pending, unanimous = [], []
+    pending, unanimous, ranked = [], [], []
+    if auc:
+        from utils.ranking import rank_metrics
     with torch.no_grad():
         for images, masks in test_loader:
             if tta is None:
@@ -252,6 +299,9 @@ def test_segmentation_model(model, test_loader, device, model_name, surface=Fals
             cnt = torch.empty(B, 4, dtype=torch.float32, device=out.device)
             lib.mi355_seg_counts(out.float().contiguous(), masks.float().contiguous(), cnt, B, per, 1 if is_logit else 0, 0.5)
             pending.append((cnt, per, _surface_raw(out, masks, is_logit, 0.5, 95, 4) if surface else None))
+            if auc:
+                rk = rank_metrics(out.float().reshape(B, per), target=masks.float().reshape(B, per), threshold=0.5)
+                ranked.append((rk["auroc"], rk["average_precision"]))
     surf = []
     if tta is not None:                           # read back with the counters below
         unanimous = torch.cat(unanimous).cpu().numpy()
@@ -270,6 +320,9 @@ def test_segmentation_model(model, test_loader, device, model_name, surface=Fals
         for k in SURFACE_KEYS:
             avg[k] = float(per_sample[k][ok].mean()) * (100.0 if k == "surface_dice" else 1.0) if ok.any() else float("nan")
         avg["surface_samples"] = int(ok.sum())
+    if auc:                                       # read back with the counters above
+        avg["pixel_auroc"], avg["auc_samples"] = _nanmean(torch.cat([a for a, _ in ranked]).cpu().numpy())
+        avg["pixel_ap"] = _nanmean(torch.cat([p for _, p in ranked]).cpu().numpy())[0]
     if tta is not None:
         avg["tta_unanimous"] = float(unanimous.mean()) * 100
         avg["tta_views"] = len(seg_tta.views)
@@ -278,6 +331,7 @@ def test_segmentation_model(model, test_loader, device, model_name, surface=Fals
     print(f"Precision:         {avg['precision']:.2f}%\nRecall:            {avg['recall']:.2f}%\nF1 Score:          {avg['f1']:.2f}%"
           + (f"\nHausdorff:         {avg['hausdorff']:.2f} px\nHD95:              {avg['hd95']:.2f} px\nASSD:              {avg['assd']:.2f} px\n"
              f"Surface Dice @2px: {avg['surface_dice']:.2f}% ({avg['surface_samples']} of {n} samples)" if surface else "")
+          + (f"\nPixel AUROC / AP:  {avg['pixel_auroc']:.4f} / {avg['pixel_ap']:.4f} ({avg['auc_samples']} of {n} samples)" if auc else "")
           + (f"\nTTA unanimous:     {avg['tta_unanimous']:.2f}% of the pixels ({avg['tta_views']} views, merged {tta_merge})" if tta is not None else "")
           + f"\n{'=' * 60}\n")
     return avg
@@ -291,7 +345,7 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", surface=False):
+                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", auc=False, calibration_bins=15, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -302,7 +356,9 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     metrics to every segmentation result (test_segmentation_model).  ``clahe=(clip, grid)``: the default loaders' transforms equalise
     the images (utils/clahe.py) — pass what the checkpoints were trained with (trainer.py --clahe-clip / --clahe-grid).  ``tta`` /
     ``tta_merge``: test-time augmentation for every model (test_classification_model(tta=...); the segmenters are handed to
-    test_segmentation_model wrapped in utils.tta.TTASegmenter)."""
+    test_segmentation_model wrapped in utils.tta.TTASegmenter).  ``auc`` / ``calibration_bins``: ROC-AUC, average precision and
+    calibration for every classifier (test_classification_model(auc=True)), per-image pixel ROC-AUC and average precision for every
+    segmenter (evaluate_segmentation_model(auc=True))."""
     from utils.helpers import get_class_model, get_seg_model
     if tta is not None:
         from utils.tta import MERGES, check_views
@@ -363,6 +419,8 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         print("Skipping classification model testing...")
     else:
         cls_test = (lambda m, l, d, name: test_classification_model(m, l, d, name, tta=tta)) if tta is not None else test_classification_model
+        if auc:
+            cls_test = lambda m, l, d, name: test_classification_model(m, l, d, name, tta=tta, auc=True, calibration_bins=calibration_bins)  # noqa: E731
         run(_CLS_FILES, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], cls_test, "Classification")
     if seg_loader is None:
         print(f"\n[WARNING] Segmentation test dataset not found: no loader given for {DATA_ROOT!r}")
@@ -374,6 +432,9 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         if tta is not None:
             from utils.tta import TTASegmenter
             seg_test = lambda m, l, d, name: test_segmentation_model(TTASegmenter(m, tta, tta_merge), l, d, name, surface=surface)  # noqa: E731
+        if auc:
+            wrap = (lambda m: TTASegmenter(m, tta, tta_merge)) if tta is not None else (lambda m: m)
+            seg_test = lambda m, l, d, name: evaluate_segmentation_model(wrap(m), l, d, name, surface=surface, auc=True)  # noqa: E731
         run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
     return results
 
@@ -397,6 +458,15 @@ def print_summary(results):
             print(f"{model:<20} {m['accuracy']:>10.2f}% {m['precision']:>10.2f}% {m['recall']:>10.2f}% {m['f1']:>10.2f}%")
         best = max(cls_models, key=lambda x: results[x]["accuracy"])
         print(f"\n\U0001F3C6 Best Classification Model: {best} (Accuracy: {results[best]['accuracy']:.2f}%)")
+        rank_models = [m for m in cls_models if all(k in results[m] for k in ("auroc", "average_precision", "ece", "brier", "nll"))]
+        if rank_models:                                     # (only after test_all_models(auc=True))
+            print("\n\nCLASSIFICATION MODELS, RANKING AND CALIBRATION (macro one-vs-rest AUROC / AP):")
+            print("-" * 80)
+            print(f"{'Model':<20} {'AUROC':<10} {'AP':<10} {'ECE':<10} {'Brier':<10} {'NLL':<10}")
+            print("-" * 80)
+            for model in rank_models:
+                m = results[model]
+                print(f"{model:<20} {m['auroc']:>8.4f}   {m['average_precision']:>8.4f}   {m['ece']:>8.4f}   {m['brier']:>8.4f}   {m['nll']:>8.4f}")
     seg_models = [m for m in ["ResNetUnet", "AttentionUNet", "R2Unet", "R2AttUnet", "CLIPSeg"] if m in results]
     if seg_models:
         print("\n\nSEGMENTATION MODELS:")
@@ -418,6 +488,15 @@ def print_summary(results):
                 m = results[model]
                 print(f"{model:<20} {m['hausdorff']:>10.2f}   {m['hd95']:>10.2f}   {m['assd']:>10.2f}   {m['surface_dice']:>11.2f}%   "
                       f"{m.get('surface_samples', ''):>7}")
+        rank_models = [m for m in seg_models if "pixel_auroc" in results[m] and "pixel_ap" in results[m]]
+        if rank_models:                                     # (only after test_all_models(auc=True))
+            print("\n\nSEGMENTATION MODELS, PIXEL RANKING (mean over the images):")
+            print("-" * 80)
+            print(f"{'Model':<20} {'Pixel AUROC':<14} {'Pixel AP':<12} {'Samples':<8}")
+            print("-" * 80)
+            for model in rank_models:
+                m = results[model]
+                print(f"{model:<20} {m['pixel_auroc']:>11.4f}   {m['pixel_ap']:>9.4f}   {m.get('auc_samples', ''):>7}")
     print("=" * 80 + "\n")
 
 
@@ -436,7 +515,7 @@ def save_results_to_csv(results, cls_output_path="results/classification_test_re
         for name in cls_models:
             row = {"Model": name}
             row.update(results[name])
-            for k in ("confusion_matrix", "precision_per_class", "recall_per_class", "f1_per_class"):
+            for k in ("confusion_matrix", "precision_per_class", "recall_per_class", "f1_per_class", "auroc_per_class", "ap_per_class"):
                 row.pop(k, None)
             rows.append(row)
         pd.DataFrame(rows).to_csv(cls_output_path, index=False)
@@ -455,7 +534,7 @@ def save_results_to_csv(results, cls_output_path="results/classification_test_re
         print("\n[INFO] No segmentation results to save.")
 
 
-if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898): same banner, same three calls
+def build_parser():
     import argparse
     _ap = argparse.ArgumentParser(description="Test every checkpoint under weights/ on the test split")
     _ap.add_argument("--surface", action="store_true", help="also report Hausdorff, HD95, ASSD and surface Dice of the segmentation models")
@@ -465,7 +544,14 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
     _ap.add_argument("--tta", choices=("hflip", "rot", "full"), default=None,
                      help="test-time augmentation: predict on these views and score the merged prediction (utils/tta.py)")
     _ap.add_argument("--tta-merge", choices=("prob", "logit"), default="prob", help="TTA: average the probabilities or the logits")
-    _args = _ap.parse_args()
+    _ap.add_argument("--auc", action="store_true",
+                     help="also report ROC-AUC and average precision (per class / per image over the pixels) and the classifiers' ECE, Brier score and NLL")
+    _ap.add_argument("--calibration-bins", type=int, default=15, help="--auc: confidence bins of the expected calibration error")
+    return _ap
+
+
+if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898): same banner, same three calls
+    _args = build_parser().parse_args()
     _kw = {}
     if _args.clahe_clip != 0:
         from utils.clahe import check_clahe
@@ -477,6 +563,8 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
         _kw["surface"] = True
     if _args.tta is not None:
         _kw.update(tta=_args.tta, tta_merge=_args.tta_merge)
+    if _args.auc:
+        _kw.update(auc=True, calibration_bins=_args.calibration_bins)
     results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
     save_results_to_csv(results, cls_output_path="classification_test_results.csv", seg_output_path="segmentation_test_results.csv")
