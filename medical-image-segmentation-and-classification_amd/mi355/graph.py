@@ -41,8 +41,7 @@ DEFER_POST = os.environ.get("MI355_DEFER_POST", "1") != "0"         # recurrent 
 
 class T:
     """NHWC activation handle: rows of C channels with channel stride ld inside `buf`."""
-    __slots__ = ("buf", "off", "N", "H", "W", "C", "ld", "_ng", "_grad", "parent", "_written", "name", "_plain_bn_relu", "_lazy_pool", "_bn_src", "_lazy_head",
-                 "_post_uses", "_post_seen", "_post_pending")
+    __slots__ = ("buf", "off", "N", "H", "W", "C", "ld", "_ng", "_grad", "parent", "_written", "name", "_bn", "_post_uses", "_post_seen", "_post_pending")
 
     def __init__(self, buf, off, N, H, W, C, ld, parent=None):
         self.buf, self.off = buf, off
@@ -52,13 +51,10 @@ class T:
         self.parent = parent
         self._written = False
         self.name = ""
-        self._plain_bn_relu = False     # relu(bn(conv(.))) with nothing added: produced by Builder.conv_bn_act in training
-        self._lazy_pool = None          # gradient of a MaxPool2d(2, 2) of this tensor left to the producer's BatchNorm backward
-        self._bn_src = None             # (raw convolution output, BatchNorm coefficient buffers) this activation was computed from
-        self._lazy_head = None          # (dz, conv): the one-channel convolution whose backward the producer's BatchNorm passes compute
+        self._bn = None                 # the BnLayer that produced this activation (Builder.conv_bn_act / bn_act)
         self._post_uses = 0             # conv_bn_act(..., post_add=this) applications in the forward plan / met so far in backward order
         self._post_seen = 0
-        self._post_pending = []         # their incoming gradients not yet added into this tensor's gradient (Builder._bn_bwd)
+        self._post_pending = []         # their incoming gradients not yet added into this tensor's gradient (Builder._bn_bwd_plain)
 
     @property
     def needs_grad(self):
@@ -126,6 +122,43 @@ class Launch:
         self.side = side          # True: may run on the plan's side stream (weight-gradient launches)
         self.cus = cus            # share of the chip's CUs the launch is sized for (1.0 unless its workgroups own CUs by design:
                                   # the eight-wave weight gradient runs on 128 of 256; bench.py's chip-time accounting)
+
+    def arg(self, name):
+        """The argument in the slot the C prototype (include/mi355conv.h) calls ``name``."""
+        return self.args[[n for _, n in lib.protos[self.name][1]].index(name)]
+
+
+class BnLayer:
+    """One ``act(bn(y) [+ res]) [+ res]`` application, both directions.  conv_bn_act() / bn_act() put the record ITSELF into
+    Builder.fwd as a placeholder (finish() lowers it once: forward_launch) and hang it on the output (``a._bn``).  Ops that ride in
+    its passes fill the mutable fields: maxpool() ``pool_out`` and logit_conv() ``head = (conv, z)`` while the record is still the
+    last forward entry, their backward rules ``pool_dp`` and ``head_dz`` (read by the layer's rule: Builder._bn_bwd_head / _pool2)."""
+    __slots__ = ("y", "st", "bn", "bias", "act", "res", "post", "a", "nbytes", "code", "rides", "pool_out", "head", "pool_dp", "head_dz")
+
+    def __init__(self, y, st, bn, bias, act, res=None, post=False, a=None, nbytes=0, code=0, rides=False):
+        self.y, self.st, self.bn, self.bias = y, st, bn, bias      # raw input, coefficient buffers, module, conv bias in front (or None)
+        self.act, self.res, self.post = act, res, post             # ReLU; the operand added before it, or AFTER it when ``post``
+        self.a, self.nbytes, self.code, self.rides = a, nbytes, code, rides      # rides: a training relu(bn(conv(.))), nothing added — a pooling's / the logit head's backward may ride
+        self.pool_out = self.head = self.pool_dp = self.head_dz = None
+
+    def forward_launch(self):
+        """The apply pass: the ONE place that decides which kernel runs it, and its algorithmic bytes."""
+        y, a, r, p, st = self.y, self.a, self.res, self.pool_out, self.st
+        esz = y.buf.element_size()
+        src = (y, y.ld, st["scale"], st["shift"])
+        dims = (a.N, a.H, a.W, a.C, (1 if self.act else 0) | (2 if self.post else 0), self.code)
+        windows = BN_ACT_WINDOWS and a.H % 2 == 0 and a.W % 2 == 0      # the window-ordered kernels: the same values, ≈8 % faster
+        if self.head is not None:       # read by the logit convolution only: mi355_gate_psi_fwd with ONE normalised operand computes it on the fly
+            conv, z = self.head
+            return Launch("mi355_gate_psi_fwd", y, y.ld, None, 0, st["scale"], st["shift"], None, None, conv.weight, conv.bias, z,
+                          None, y.M, y.C, self.code, nbytes=y.M * y.C * esz + 4 * y.M)
+        if p is not None:               # the MaxPool2d(2, 2) that follows leaves the same pass: no re-read of the activation
+            return Launch("mi355_bn_act_pool2", *src, a, a.ld, p, p.ld, *dims, nbytes=self.nbytes + p.M * p.C * esz)
+        if windows and r is None:
+            return Launch("mi355_bn_act_pool2", *src, a, a.ld, None, 0, *dims, nbytes=self.nbytes)
+        if windows and BN_ACT_WINDOWS_RES:      # residual added before / after the activation (ResNet.py:43, R2AttU_Net.py:44)
+            return Launch("mi355_bn_act_windows", *src, r, r.ld, a, a.ld, *dims, nbytes=self.nbytes)
+        return Launch("mi355_bn_act", *src, None, 0, None, None, r, r.ld if r is not None else 0, a, a.ld, y.M, y.C, *dims[4:], nbytes=self.nbytes)
 
 
 class Plan:
@@ -382,6 +415,7 @@ class Builder:
         self._rules = []                 # closures, run in reverse at finish()
         self._conv_uses = {}             # id(conv) -> forward applications (recurrent blocks share a conv)
         self._pending_wgrad = {}         # id(conv) -> [(x, dy)] waiting for the other applications' backward
+        self._post_operands = []         # tensors used as conv_bn_act(..., post_add=): finish() checks their bookkeeping
         self.multi_wgrad = os.environ.get("MI355_WGRAD_MULTI", "1") != "0"
         self.keep = []
         self.ws_need = {"bytes": 0, "f32": 0}
@@ -599,9 +633,9 @@ class Builder:
         return k, s, p, (hl + 2 * p - k) // s + 1, (wl + 2 * p - k) // s + 1
 
     def conv_raw(self, x, conv, up=False, out=None, stats=False, relu=False, fold=None):
-        """y = conv(x) (+bias), raw output in the compute dtype; returns (y, bwd(dy, bias_done)).  With
+        """y = conv(x) (+bias), raw output in the compute dtype; returns (y, bwd(dy, bias_done), stat_rows).  With
         ``stats`` the BatchNorm partial sums of y are produced by the conv epilogue when the kernel supports
-        it (``self._last_stat_rows`` > 0 afterwards).  ``relu``: max(0, .) in the epilogue.  ``fold = (scale, bias)``:
+        it: ``stat_rows`` > 0 partial rows wait in the f32 workspace (_bn_coeffs' ``fused_rows``).  ``relu``: max(0, .) in the epilogue.  ``fold = (scale, bias)``:
         eval-mode BatchNorm folded into the packed weights and the bias (forward-only plans)."""
         stem = self._stem_as_pointwise(x, conv, up)
         if stem is not None:
@@ -618,14 +652,12 @@ class Builder:
         flops = 2 * x.N * Ho * Wo * Co * k * k * conv.in_channels
         # algorithmic HBM bytes of one conv launch: input read once, output written once, weights read once
         nbytes = (x.N * x.H * x.W * x.C + x.N * Ho * Wo * Co + Co * k * k * x.C) * self.esz
-        stat_part = None
-        self._last_stat_rows = 0
+        stat_part, stat_rows = None, 0
         geom = (x.N, x.H, x.W, x.C, Ho, Wo, Co, k, k, s, 1, -p, 1, 1 if up else 0)
         if stats and self.training:
-            rows = lib.mi355_conv2d_igemm_stat_rows(*geom, self.code)
-            if rows > 0:            # the kernel serving this shape folds the BatchNorm statistics into its epilogue
-                stat_part = self.ws_f32(rows * 2 * Co)
-                self._last_stat_rows = rows
+            stat_rows = max(0, lib.mi355_conv2d_igemm_stat_rows(*geom, self.code))
+            if stat_rows:           # the kernel serving this shape folds the BatchNorm statistics into its epilogue
+                stat_part = self.ws_f32(stat_rows * 2 * Co)
         self.fwd.append(self.igemm(x, wf, bias, y, geom, 2 if relu else 0, stat_part, flops=flops, nbytes=nbytes))
         y.needs_grad = x.needs_grad or self.param_grad(conv.weight)
         self._conv_uses[id(conv)] = self._conv_uses.get(id(conv), 0) + 1
@@ -667,7 +699,7 @@ class Builder:
                     tmp = self.new_tensor(x.N, hg, wg, x.C)
                     self.bwd.append(self.igemm(dy, wb, None, tmp, dgeom, 0, flops=flops, nbytes=nbytes))
                     self.bwd.append(Launch("mi355_upsample2_bwd", tmp, tmp.ld, xg, xg.ld, x.N, x.H, x.W, x.C, acc, self.code))
-        return y, bwd
+        return y, bwd, stat_rows
 
     def _emit_multi_wgrad(self, conv, pend, Ho, Wo, Co, k, up, flops, nbytes):
         x0 = pend[0][0]
@@ -742,94 +774,94 @@ class Builder:
                                    C, st["scale"], st["shift"]))
         return st
 
-    def _bn_bwd(self, da, a, y, bn, st, act, dres_to=None, bias=None, post_to=None, pool_dp=None, head=None):
-        """Emit BN(+ReLU) backward: returns dy (grad of the raw input y).  ``pool_dp``: the gradient of a MaxPool2d(2, 2) of the
-        activation that maxpool() left for these passes to add on the fly (no mi355_maxpool_bwd pass over da)."""
+    def _bn_param_grads(self, bn, part, rows, *at):
+        """Register the BatchNorm's parameter gradients and emit the fold of ``rows`` partial rows into them and into ``sums``
+        (returned): mi355_bn_bwd_finalize, or _at with ``at = (nq, q0, q1)``: rows of nq quantities, (sum g, sum g*xhat) at (q0, q1).
+        The ORDER of pgrad() calls in the BatchNorm backward is part of the contract — a head's weight and bias, gamma, beta, then the
+        conv bias (_zero_bias_grad): it defines plan.grad_params, zero_grad_params, last_write and every first-write beta."""
         C = bn.num_features
-        nb = lib.mi355_rowreduce_blocks(y.M)
-        part = self.ws_f32(nb * 2 * C)
-        if head is not None:
-            # relu(bn(y)) feeds ONLY a one-channel 1x1 convolution (the logit head): its gradient dz[m] * w[c] * [a > 0] is recomputed
-            # from dz and y by the attention gate's two-pass kernels with ONE normalised operand; the same passes leave the head's
-            # weight / bias gradients (mi355_rowdot_bwd and the stored activation and its stored gradient all disappear)
-            dz, hconv = head
-            assert act and dres_to is None and post_to is None and pool_dp is None
-            part = self.f32(nb * 5 * C) if SIDE_COLSUM else self.ws_f32(nb * 5 * C)      # (its own buffer: read from the side stream)
-            co = (st["scale"], st["shift"], st["mean"], st["invstd"], None, None, None, None)
-            self.bwd.append(Launch("mi355_gate_bn_bwd_reduce", dz, y, y.ld, None, 0, *co, hconv.weight, part, y.M, C, self.code,
-                                   nbytes=y.M * C * self.esz + 4 * y.M))
-            head_folds = []
-            if self.param_grad(hconv.weight):
-                wref, wbeta = self.pgrad(hconv.weight)
-                head_folds.append(Launch("mi355_colsum_finalize", self._ws_off(part, 3 * C * 4), nb, 5, C, wref, wbeta, side=SIDE_COLSUM))
-                if hconv.bias is not None:
-                    bref2, bbeta = self.pgrad(hconv.bias)
-                    head_folds.append(Launch("mi355_colsum_finalize", self._ws_off(part, 4 * C * 4), nb, 5 * C, 1, bref2, bbeta, side=SIDE_COLSUM))
-            sums = self.f32(2 * C)
-            need_pg = self.param_grad(bn.weight)
-            if need_pg:
-                gref, gbeta = self.pgrad(bn.weight)
-                bref, _ = self.pgrad(bn.bias)
-            self.bwd.append(Launch("mi355_bn_bwd_finalize_at", part, min(nb, lib.mi355_gate_bn_bwd_reduce_rows(y.M)), 5, 0, 1, C, sums,
-                                   gref if need_pg else None, bref if need_pg else None, gbeta if need_pg else 0.0))
-            if bias is not None and self.param_grad(bias) and id(bias) not in self._grad_first:
-                self.pgrad(bias)
-                self.zero_grad_params.append(bias)
-            dy = self.grad_of(y)
-            self.bwd.append(Launch("mi355_gate_bn_bwd_apply", dz, y, y.ld, None, 0, *co, hconv.weight, bn.weight, None, sums, None,
-                                   dy, dy.ld, None, 0, y.M, C, self.code, nbytes=2 * y.M * C * self.esz + 4 * y.M))
-            self.bwd += head_folds        # (they only feed the optimiser: behind the apply pass, off the main stream)
-            return dy
-        if pool_dp is not None:
-            assert act and dres_to is None and post_to is None
-            dal = da.ld if da is not None else 0          # (da None: the pooled gradient is the activation's whole gradient)
-            self.bwd.append(Launch("mi355_bn_bwd_reduce_pool2", da, dal, pool_dp, pool_dp.ld, y, y.ld, st["mean"], st["invstd"],
-                                   st["scale"], st["shift"], part, y.N, y.H, y.W, C, self.code,
-                                   nbytes=int((1.25 + (da is not None)) * y.M * C * self.esz)))
-            sums = self.f32(2 * C)
-            need_pg = self.param_grad(bn.weight)
-            if need_pg:
-                gref, gbeta = self.pgrad(bn.weight)
-                bref, _ = self.pgrad(bn.bias)
-            self.bwd.append(Launch("mi355_bn_bwd_finalize", part, min(nb, lib.mi355_bn_bwd_reduce_pool2_rows(y.M)), C, sums,
-                                   gref if need_pg else None, bref if need_pg else None, gbeta if need_pg else 0.0))
-            dy = self.grad_of(y)
-            if bias is not None and self.param_grad(bias) and id(bias) not in self._grad_first:
-                self.pgrad(bias)
-                self.zero_grad_params.append(bias)
-            self.bwd.append(Launch("mi355_bn_bwd_apply_pool2", da, dal, pool_dp, pool_dp.ld, y, y.ld, bn.weight, st["mean"],
-                                   st["invstd"], st["scale"], st["shift"], sums, dy, dy.ld, y.N, y.H, y.W, C, self.code,
-                                   nbytes=int((2.25 + (da is not None)) * y.M * C * self.esz)))
-            return dy
-        # the ReLU mask is recomputed from the raw input with the forward's coefficients unless something was
-        # added in front of the ReLU (residual / second operand), in which case the activated tensor is read
-        am = a if (act and dres_to is not None) else None
-        self.bwd.append(Launch("mi355_bn_bwd_reduce", da, da.ld, am, am.ld if am is not None else 0, y, y.ld,
-                               st["mean"], st["invstd"], st["scale"], st["shift"], part, y.M, C, 1 if act else 0, self.code,
-                               nbytes=(2 + (am is not None)) * y.M * C * self.esz))
         sums = self.f32(2 * C)
-        need_pg = self.param_grad(bn.weight)
-        if need_pg:
+        gref, bref, gbeta = None, None, 0.0
+        if self.param_grad(bn.weight):
             gref, gbeta = self.pgrad(bn.weight)
             bref, _ = self.pgrad(bn.bias)
-        # (the reduction runs on at most 256 workgroups — rowred.hpp, ops that keep several rows in flight — and zero-fills the partial
-        # rows beyond its grid: the fold only has to read the rows that can be non-zero)
-        nb_fold = min(nb, lib.mi355_bn_bwd_reduce_rows(y.M))
-        self.bwd.append(Launch("mi355_bn_bwd_finalize", part, nb_fold, C, sums, gref if need_pg else None,
-                               bref if need_pg else None, gbeta if need_pg else 0.0))
-        dy = self.grad_of(y)
-        dres = None
-        if dres_to is not None and dres_to.needs_grad:
-            if self.acc_flag(dres_to):
-                dres = self.new_tensor(y.N, y.H, y.W, C)      # accumulate through a temporary
-            else:
-                dres = self.grad_of(dres_to)
-        # The gradient of a conv bias that feeds a train-mode BatchNorm is exactly zero (sum_m dy = 0 because
-        # sum_m xhat = 0); torch computes ~1e-9 of round-off there.  It is not computed: the slot in the flat
-        # gradient buffer stays at its initial zero, the parameter is still registered as "has a gradient".
+        self.bwd.append(Launch("mi355_bn_bwd_finalize_at" if at else "mi355_bn_bwd_finalize", part, rows, *at, C, sums, gref, bref, gbeta))
+        return sums
+
+    def _zero_bias_grad(self, bias):
+        """The gradient of a conv bias that feeds a train-mode BatchNorm is exactly zero (sum_m dy = 0 because sum_m xhat = 0);
+        torch computes ~1e-9 of round-off there.  It is not computed: the slot in the flat gradient buffer stays at its initial
+        zero, the parameter is still registered as "has a gradient"."""
         if bias is not None and self.param_grad(bias) and id(bias) not in self._grad_first:
             self.pgrad(bias)
             self.zero_grad_params.append(bias)
+
+    def _bn_bwd_head(self, rec):
+        """relu(bn(y)) feeds ONLY a one-channel 1x1 convolution (the logit head): its gradient dz[m] * w[c] * [a > 0] is recomputed
+        from dz and y by the attention gate's two-pass kernels with ONE normalised operand; the same passes leave the head's weight /
+        bias gradients (mi355_rowdot_bwd and the stored activation and its stored gradient all disappear).  Returns dy."""
+        y, bn, st, dz, hconv = rec.y, rec.bn, rec.st, rec.head_dz, rec.head[0]
+        C = bn.num_features
+        nb = lib.mi355_rowreduce_blocks(y.M)
+        part = self.f32(nb * 5 * C) if SIDE_COLSUM else self.ws_f32(nb * 5 * C)      # (its own buffer: read from the side stream)
+        co = (st["scale"], st["shift"], st["mean"], st["invstd"], None, None, None, None)
+        self.bwd.append(Launch("mi355_gate_bn_bwd_reduce", dz, y, y.ld, None, 0, *co, hconv.weight, part, y.M, C, self.code, nbytes=y.M * C * self.esz + 4 * y.M))
+        head_folds = []
+        if self.param_grad(hconv.weight):
+            wref, wbeta = self.pgrad(hconv.weight)
+            head_folds.append(Launch("mi355_colsum_finalize", self._ws_off(part, 3 * C * 4), nb, 5, C, wref, wbeta, side=SIDE_COLSUM))
+            if hconv.bias is not None:
+                bref, bbeta = self.pgrad(hconv.bias)
+                head_folds.append(Launch("mi355_colsum_finalize", self._ws_off(part, 4 * C * 4), nb, 5 * C, 1, bref, bbeta, side=SIDE_COLSUM))
+        sums = self._bn_param_grads(bn, part, min(nb, lib.mi355_gate_bn_bwd_reduce_rows(y.M)), 5, 0, 1)
+        self._zero_bias_grad(rec.bias)
+        dy = self.grad_of(y)
+        self.bwd.append(Launch("mi355_gate_bn_bwd_apply", dz, y, y.ld, None, 0, *co, hconv.weight, bn.weight, None, sums, None,
+                               dy, dy.ld, None, 0, y.M, C, self.code, nbytes=2 * y.M * C * self.esz + 4 * y.M))
+        self.bwd += head_folds        # (they only feed the optimiser: behind the apply pass, off the main stream)
+        return dy
+
+    def _bn_bwd_pool2(self, rec, da):
+        """BatchNorm + ReLU backward that adds ``rec.pool_dp``, the gradient of a MaxPool2d(2, 2) of the activation, on the fly (no
+        mi355_maxpool_bwd pass over da).  ``da`` None: the pooled gradient is the activation's whole gradient.  Returns dy."""
+        y, bn, st, dp = rec.y, rec.bn, rec.st, rec.pool_dp
+        assert rec.act and rec.res is None
+        C = bn.num_features
+        nb = lib.mi355_rowreduce_blocks(y.M)
+        part = self.ws_f32(nb * 2 * C)
+        ops = (da, da.ld if da is not None else 0, dp, dp.ld, y, y.ld)
+        co, dims = (st["mean"], st["invstd"], st["scale"], st["shift"]), (y.N, y.H, y.W, C, self.code)
+        self.bwd.append(Launch("mi355_bn_bwd_reduce_pool2", *ops, *co, part, *dims, nbytes=int((1.25 + (da is not None)) * y.M * C * self.esz)))
+        sums = self._bn_param_grads(bn, part, min(nb, lib.mi355_bn_bwd_reduce_pool2_rows(y.M)))
+        dy = self.grad_of(y)
+        self._zero_bias_grad(rec.bias)
+        self.bwd.append(Launch("mi355_bn_bwd_apply_pool2", *ops, bn.weight, *co, sums, dy, dy.ld, *dims,
+                               nbytes=int((2.25 + (da is not None)) * y.M * C * self.esz)))
+        return dy
+
+    def _bn_bwd_plain(self, rec, da):
+        """BatchNorm (+ReLU) backward in two passes, with the gradients of a residual (added before the ReLU) or of a post-activation
+        operand (``rec.post``) leaving the apply pass.  Returns dy, the gradient of the raw input."""
+        y, bn, st, act = rec.y, rec.bn, rec.st, rec.act
+        dres_to, post_to = (None, rec.res) if rec.post else (rec.res, None)
+        C = bn.num_features
+        nb = lib.mi355_rowreduce_blocks(y.M)
+        part = self.ws_f32(nb * 2 * C)
+        # the ReLU mask is recomputed from the raw input with the forward's coefficients unless something was
+        # added in front of the ReLU (residual / second operand), in which case the activated tensor is read
+        am = rec.a if (act and dres_to is not None) else None
+        ops = (da, da.ld, am, am.ld if am is not None else 0, y, y.ld)
+        co, dims = (st["mean"], st["invstd"], st["scale"], st["shift"]), (y.M, C, 1 if act else 0, self.code)
+        self.bwd.append(Launch("mi355_bn_bwd_reduce", *ops, *co, part, *dims, nbytes=(2 + (am is not None)) * y.M * C * self.esz))
+        # (the reduction runs on at most 256 workgroups — rowred.hpp, ops that keep several rows in flight — and zero-fills the partial
+        # rows beyond its grid: the fold only has to read the rows that can be non-zero)
+        sums = self._bn_param_grads(bn, part, min(nb, lib.mi355_bn_bwd_reduce_rows(y.M)))
+        dy = self.grad_of(y)
+        ops += (bn.weight, *co, sums, dy, dy.ld)
+        dres = None
+        if dres_to is not None and dres_to.needs_grad:      # (the first contribution is written in place, later ones go through a temporary)
+            dres = self.new_tensor(y.N, y.H, y.W, C) if self.acc_flag(dres_to) else self.grad_of(dres_to)
+        self._zero_bias_grad(rec.bias)
         # an operand added AFTER the activation (recurrent block x + relu(bn(.))) receives the incoming gradient itself: the
         # apply pass reads it anyway and writes / accumulates it (no separate mi355_add pass over da)
         pg, pacc = None, 0
@@ -846,19 +878,14 @@ class Builder:
                 pacc = self.acc_flag(post_to)
                 pg = self.grad_of(post_to)
                 if pend:
+                    assert dres is None
                     ex = pend + [None] * (4 - len(pend))
-                    self.bwd.append(Launch("mi355_bn_bwd_apply_post4", da, da.ld, am, am.ld if am is not None else 0, y, y.ld, bn.weight,
-                                           st["mean"], st["invstd"], st["scale"], st["shift"], sums, dy, dy.ld, pg, pg.ld,
-                                           1 if pacc else 0, *ex, pend[0].ld, y.M, C, 1 if act else 0, self.code,
+                    self.bwd.append(Launch("mi355_bn_bwd_apply_post4", *ops, pg, pg.ld, 1 if pacc else 0, *ex, pend[0].ld, *dims,
                                            nbytes=(4 + (am is not None) + (1 if pacc else 0) + len(pend)) * y.M * C * self.esz))
                     post_to._post_pending = []
-                    assert dres is None
                     return dy
-        self.bwd.append(Launch("mi355_bn_bwd_apply", da, da.ld, am, am.ld if am is not None else 0, y, y.ld, bn.weight,
-                               st["mean"], st["invstd"], st["scale"], st["shift"], sums, dy, dy.ld,
-                               dres, dres.ld if dres is not None else 0, pg, pg.ld if pg is not None else 0, 1 if pacc else 0,
-                               None, y.M, C, 1 if act else 0, self.code,
-                               nbytes=(3 + (am is not None) + (dres is not None) + (pg is not None) * (2 if pacc else 1)) * y.M * C * self.esz))
+        self.bwd.append(Launch("mi355_bn_bwd_apply", *ops, dres, dres.ld if dres is not None else 0, pg, pg.ld if pg is not None else 0,
+                               1 if pacc else 0, None, *dims, nbytes=(3 + (am is not None) + (dres is not None) + (pg is not None) * (2 if pacc else 1)) * y.M * C * self.esz))
         if dres is not None and dres is not dres_to._grad:
             rg = self.grad_of(dres_to)
             self.bwd.append(Launch("mi355_add", rg, rg.ld, dres, dres.ld, rg, rg.ld, y.M, C, self.code))
@@ -887,36 +914,33 @@ class Builder:
             self.pre.append(Launch("mi355_bn_eval_coeffs", bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps),
                                    bn.num_features, sc, sh))
             self.pre.append(Launch("mi355_bn_fold_bias", conv.bias, sc, sh, fb, bn.num_features))
-            a, _ = self.conv_raw(x, conv, up, out=out, relu=act, fold=(sc, fb))
+            a, _, _ = self.conv_raw(x, conv, up, out=out, relu=act, fold=(sc, fb))
             a.needs_grad = False
             return a
         if post_add is not None:
+            if not post_add._post_uses:
+                self._post_operands.append(post_add)
             post_add._post_uses += 1
-        y, conv_bwd = self.conv_raw(x, conv, up, stats=True)
-        st = self._bn_coeffs(y, bn, self._last_stat_rows)
+        y, conv_bwd, stat_rows = self.conv_raw(x, conv, up, stats=True)
+        st = self._bn_coeffs(y, bn, stat_rows)
         a = out if out is not None else self.new_tensor(y.N, y.H, y.W, y.C)
         r = res if res is not None else post_add
-        flags = (1 if act else 0) | (2 if post_add is not None else 0)
-        self.fwd.append(Launch("mi355_bn_act", y, y.ld, st["scale"], st["shift"], None, 0, None, None,
-                               r, r.ld if r is not None else 0, a, a.ld, y.M, y.C, flags, self.code,
-                               nbytes=(2 + (r is not None)) * y.M * y.C * self.esz))
+        rec = a._bn = BnLayer(y, st, bn, conv.bias, act, r, post_add is not None, a, (2 + (r is not None)) * y.M * y.C * self.esz, self.code,
+                              rides=bool(act and r is None and self.training))
+        self.fwd.append(rec)
         a.needs_grad = y.needs_grad or self.param_grad(bn.weight) or (r is not None and r.needs_grad)
         if act:
             self.acts.append(("relu", a) if post_add is None else ("relu_pre", y, st["scale"], st["shift"]))
-        a._plain_bn_relu = bool(act and r is None and self.training)      # (maxpool(): its gradient may ride in this layer's backward)
-        a._bn_src = (y, st)
 
         def rule():
             if not a.needs_grad:
                 return
-            if a._lazy_head is not None:      # logit_conv(): the gradient of `a` is dz[m] * w[c], recomputed inside the two passes
-                dy = self._bn_bwd(None, a, y, bn, st, act, bias=conv.bias, head=a._lazy_head)
-            elif a._lazy_pool is not None and not self.grad_written(a):      # the pooling was the only consumer: its routed gradient alone
-                dy = self._bn_bwd(None, a, y, bn, st, act, bias=conv.bias, pool_dp=a._lazy_pool)
-            else:
-                da = self.grad_of(a)
-                # d(x + relu(.)) / dx = identity: folded into the BatchNorm apply pass
-                dy = self._bn_bwd(da, a, y, bn, st, act, dres_to=res, bias=conv.bias, post_to=post_add, pool_dp=a._lazy_pool)
+            if rec.head_dz is not None:       # logit_conv(): the gradient of `a` is dz[m] * w[c], recomputed inside the two passes
+                dy = self._bn_bwd_head(rec)
+            elif rec.pool_dp is not None:     # maxpool(): (the pooling was the only consumer: its routed gradient alone)
+                dy = self._bn_bwd_pool2(rec, self.grad_of(a) if self.grad_written(a) else None)
+            else:                             # (d(x + relu(.)) / dx = identity: folded into the BatchNorm apply pass)
+                dy = self._bn_bwd_plain(rec, self.grad_of(a))
             conv_bwd(dy, bias_done=True)
         self.rule(rule)
         return a
@@ -925,8 +949,8 @@ class Builder:
         """Stand-alone BatchNorm (+ReLU) on an activation (ResNet.py:134: bn1 applied a second time)."""
         st = self._bn_coeffs(x, bn)
         a = out if out is not None else self.new_tensor(x.N, x.H, x.W, x.C)
-        self.fwd.append(Launch("mi355_bn_act", x, x.ld, st["scale"], st["shift"], None, 0, None, None, None, 0, a, a.ld,
-                               x.M, x.C, 1 if act else 0, self.code))
+        rec = a._bn = BnLayer(x, st, bn, None, act, a=a, code=self.code)
+        self.fwd.append(rec)
         a.needs_grad = x.needs_grad or self.param_grad(bn.weight)
 
         def rule():
@@ -935,13 +959,13 @@ class Builder:
             da = self.grad_of(a)
             if x.needs_grad and self.acc_flag(x):
                 raise NotImplementedError("bn_act input with several consumers")
-            self._bn_bwd(da, a, x, bn, st, act)
+            self._bn_bwd_plain(rec, da)
         self.rule(rule)
         return a
 
     def conv_act(self, x, conv, relu=False, up=False, out=None):
         """conv (+bias) with optional ReLU and no normalisation (VGG.py:9-41; R2AttU_Net.py:54)."""
-        y, conv_bwd = self.conv_raw(x, conv, up, out=out, relu=relu)        # ReLU rides in the conv epilogue
+        y, conv_bwd, _ = self.conv_raw(x, conv, up, out=out, relu=relu)     # ReLU rides in the conv epilogue
         if not relu:
             def rule():
                 if y.needs_grad:
@@ -1000,14 +1024,12 @@ class Builder:
     def maxpool(self, x, k=2, s=2, p=0):
         Ho, Wo = (x.H + 2 * p - k) // s + 1, (x.W + 2 * p - k) // s + 1
         y = self.new_tensor(x.N, Ho, Wo, x.C)
-        last = self.fwd[-1] if self.fwd else None
-        if (FUSE_POOL and (k, s, p) == (2, 2, 0) and x.H % 2 == 0 and x.W % 2 == 0 and last is not None and last.name == "mi355_bn_act"
-                and last.args[10] is x and last.args[4] is None and last.args[8] is None and last.args[12] == x.M):
+        rec = x._bn
+        if (FUSE_POOL and (k, s, p) == (2, 2, 0) and x.H % 2 == 0 and x.W % 2 == 0 and rec is not None and self.fwd[-1] is rec
+                and rec.res is None and rec.pool_out is None and rec.head is None):
             # the pooled tensor leaves the BatchNorm apply pass that has just produced x (a plain one: no second operand, no
             # residual): one read of the raw convolution output instead of that plus a re-read of the activation
-            a = last.args
-            self.fwd[-1] = Launch("mi355_bn_act_pool2", a[0], a[1], a[2], a[3], x, x.ld, y, y.ld, x.N, x.H, x.W, x.C, a[14], self.code,
-                                  nbytes=last.bytes + y.M * y.C * self.esz)
+            rec.pool_out = y
         else:
             self.fwd.append(Launch("mi355_maxpool_fwd", x, x.ld, y, y.ld, x.N, x.H, x.W, x.C, k, s, p, self.code))
         self.acts.append(("pool", x, y, k, s, p))
@@ -1017,13 +1039,13 @@ class Builder:
             if not y.needs_grad:
                 return
             dy = self.grad_of(y)
-            if (FUSE_POOL_BWD and (k, s, p) == (2, 2, 0) and getattr(x, "_plain_bn_relu", False)
+            if (FUSE_POOL_BWD and (k, s, p) == (2, 2, 0) and x._bn is not None and x._bn.rides
                     and lib.mi355_bn_bwd_pool2_ok(x.H, x.W, x.C, self.code)):
                 # x = relu(bn(conv(.))): the layer's two BatchNorm backward passes add the pooled gradient on the fly instead of a
                 # scatter pass over dx — on top of the other consumers' parts (a U-Net's skip: they come later in the forward, so
                 # they are in dx by then), or ALONE when the pooling is the only consumer (VGG.py's feature stack): conv_bn_act's
                 # rule looks whether anything has been written
-                x._lazy_pool = dy
+                x._bn.pool_dp = dy
                 return
             acc = self.acc_flag(x)
             xg = self.grad_of(x)
@@ -1078,10 +1100,10 @@ class Builder:
         cp, bp = att.psi[0], att.psi[1]
         F_int = cg.out_channels
         M = x.M
-        g1, g1_bwd = self.conv_raw(g, cg, stats=True)
-        sg = self._bn_coeffs(g1, bg, self._last_stat_rows)
-        x1, x1_bwd = self.conv_raw(x, cx, stats=True)
-        sx = self._bn_coeffs(x1, bx, self._last_stat_rows)
+        g1, g1_bwd, g1_rows = self.conv_raw(g, cg, stats=True)
+        sg = self._bn_coeffs(g1, bg, g1_rows)
+        x1, x1_bwd, x1_rows = self.conv_raw(x, cx, stats=True)
+        sx = self._bn_coeffs(x1, bx, x1_rows)
         # psi_in = relu(bn(g1) + bn(x1)) is not materialised when both directions recompute it from the raw branch outputs
         fused = FUSE_GATE_BWD and bool(lib.mi355_gate_psi_fwd_ok(F_int, self.code))
         z = self.f32(M)
@@ -1156,17 +1178,8 @@ class Builder:
                 nbf = min(nb, lib.mi355_gate_bn_bwd_reduce_rows(M))
                 sums = []
                 for q1, bn_, bias_ in ((1, bg, cg.bias), (2, bx, cx.bias)):
-                    sm = self.f32(2 * F_int)
-                    need_pg = self.param_grad(bn_.weight)
-                    if need_pg:
-                        gref_, gbeta_ = self.pgrad(bn_.weight)
-                        bref_, _ = self.pgrad(bn_.bias)
-                    self.bwd.append(Launch("mi355_bn_bwd_finalize_at", part3, nbf, 5, 0, q1, F_int, sm, gref_ if need_pg else None,
-                                           bref_ if need_pg else None, gbeta_ if need_pg else 0.0))
-                    if bias_ is not None and self.param_grad(bias_) and id(bias_) not in self._grad_first:      # (see _bn_bwd)
-                        self.pgrad(bias_)
-                        self.zero_grad_params.append(bias_)
-                    sums.append(sm)
+                    sums.append(self._bn_param_grads(bn_, part3, nbf, 5, 0, q1))
+                    self._zero_bias_grad(bias_)
                 dg1, dx1 = self.grad_of(g1), self.grad_of(x1)
                 self.bwd.append(Launch("mi355_gate_bn_bwd_apply", dz, g1, g1.ld, x1, x1.ld, *co, cp.weight, bg.weight, bx.weight,
                                        sums[0], sums[1], dg1, dg1.ld, dx1, dx1.ld, M, F_int, self.code,
@@ -1184,10 +1197,8 @@ class Builder:
             self.bwd.append(Launch("mi355_colsum_finalize", part3, nb, 2, F_int, wref, wbeta))
             self.bwd.append(Launch("mi355_colsum_finalize", self._ws_off(part3, F_int * 4), nb, 2 * F_int, 1, bref2, bbeta))
             # the two normalised branches share dp
-            dg1 = self._bn_bwd(dp, None, g1, bg, sg, False, bias=cg.bias)
-            g1_bwd(dg1, bias_done=True)
-            dx1 = self._bn_bwd(dp, None, x1, bx, sx, False, bias=cx.bias)
-            x1_bwd(dx1, bias_done=True)
+            g1_bwd(self._bn_bwd_plain(BnLayer(g1, sg, bg, cg.bias, False), dp), bias_done=True)
+            x1_bwd(self._bn_bwd_plain(BnLayer(x1, sx, bx, cx.bias, False), dp), bias_done=True)
         self.rule(rule)
         return y
 
@@ -1199,17 +1210,15 @@ class Builder:
         M, K, C, HW = x.M, conv.out_channels, x.C, x.H * x.W
         z = self.f32(M * K)
         self.see(conv.weight, conv.bias)
-        last = self.fwd[-1] if self.fwd else None
-        fused = (FUSE_HEAD and K == 1 and x._plain_bn_relu and x._bn_src is not None and last is not None and last.name == "mi355_bn_act"
-                 and last.args[10] is x and self.acts and self.acts[-1] == ("relu", x) and bool(lib.mi355_gate_psi_fwd_ok(C, self.code))
+        rec = x._bn
+        fused = (FUSE_HEAD and K == 1 and rec is not None and rec.rides and self.fwd[-1] is rec and rec.pool_out is None and rec.head is None
+                 and self.acts and self.acts[-1] == ("relu", x) and bool(lib.mi355_gate_psi_fwd_ok(C, self.code))
                  and (x.needs_grad or not self.param_grad(conv.weight)))      # (the head's weight gradient comes out of the layer's backward passes)
         if fused:
-            # x = relu(bn(y)) is read by this convolution only: one pass over y computes it on the fly (mi355_gate_psi_fwd with one
-            # normalised operand) — the activation is stored in neither direction (the backward recomputes it from y as well)
-            y, st = x._bn_src
-            self.fwd[-1] = Launch("mi355_gate_psi_fwd", y, y.ld, None, 0, st["scale"], st["shift"], None, None, conv.weight, conv.bias, z,
-                                  None, M, C, self.code, nbytes=M * C * self.esz + 4 * M)
-            self.acts[-1] = ("relu_pre", y, st["scale"], st["shift"])
+            # x = relu(bn(y)) is read by this convolution only: the layer's apply pass computes the logits instead, and the activation
+            # is stored in neither direction (the backward recomputes it from y as well)
+            rec.head = (conv, z)
+            self.acts[-1] = ("relu_pre", rec.y, rec.st["scale"], rec.st["shift"])
         else:
             for k in range(K):
                 self.fwd.append(Launch("mi355_rowdot_fwd", x, x.ld, (conv.weight, k * C * 4), (conv.bias, k * 4) if conv.bias is not None else None,
@@ -1223,7 +1232,7 @@ class Builder:
             if not needs:
                 return
             if fused:
-                x._lazy_head = (self.dout, conv)      # conv_bn_act's rule (it runs next) emits the two passes
+                rec.head_dz = self.dout      # conv_bn_act's rule (it runs next) emits the two passes
                 return
             nb = lib.mi355_rowreduce_blocks(M)
             dx = None
@@ -1405,20 +1414,7 @@ class Builder:
 
     # ---- finish -------------------------------------------------------------------------------------------------------------
     def finish(self):
-        if BN_ACT_WINDOWS:
-            # plain BatchNorm apply passes on even images (no second operand, no residual, not absorbed by a pooling / gate / head
-            # peephole meanwhile): the window-ordered kernel without a pooled output — the same values, ≈8 % faster
-            for i, l in enumerate(self.fwd):
-                a_ = l.args
-                if l.name == "mi355_bn_act" and a_[4] is None and isinstance(a_[10], T) and a_[10].H % 2 == 0 \
-                        and a_[10].W % 2 == 0 and a_[12] == a_[10].M:
-                    t = a_[10]
-                    if a_[8] is None:
-                        self.fwd[i] = Launch("mi355_bn_act_pool2", a_[0], a_[1], a_[2], a_[3], t, t.ld, None, 0, t.N, t.H, t.W, t.C, a_[14],
-                                             self.code, nbytes=l.bytes)
-                    elif BN_ACT_WINDOWS_RES:      # residual added before / after the activation (ResNet.py:43, R2AttU_Net.py:44)
-                        self.fwd[i] = Launch("mi355_bn_act_windows", a_[0], a_[1], a_[2], a_[3], a_[8], a_[9], t, t.ld, t.N, t.H, t.W, t.C,
-                                             a_[14], self.code, nbytes=l.bytes)
+        self.fwd = [l.forward_launch() if isinstance(l, BnLayer) else l for l in self.fwd]
         if getattr(self, "_xcol", None) is not None:
             # the stem reads the im2col of the input: that pack takes the place of the plain one as launch 0 (the launch whose source
             # pointer Plan.run_forward patches to the caller's tensor)
@@ -1460,6 +1456,8 @@ class Builder:
             self.cam_lowres = self.f32(t.N * t.H * t.W)
             self.bwd.append(Launch("mi355_gradcam", t, t.ld, g, g.ld, t.N, t.H * t.W, t.C, self.code, self.cam_lowres))
         assert not self._pending_wgrad, "a shared convolution's weight gradient is still waiting for an application's backward"
+        assert not self.want_grad or all(not t._post_pending and t._post_seen == (t._post_uses if t.needs_grad else 0)
+                                         for t in self._post_operands), "a post_add operand's gradient lacks an application's incoming gradient"
         # The side launches BEHIND the last main-stream launch of the backward (the first layer's weight gradient and its reduce)
         # have nothing left to overlap with: on the side stream they only put a cross-queue join (~50 us until the main queue sees the
         # side queue's signal, production trace profiles/r04d_trace_step_timeline.txt) in front of the optimiser.  They run on the
@@ -1474,8 +1472,8 @@ class Builder:
                 tail.append(l)
             need = 0
             for l in tail:
-                if l.name == "mi355_conv2d_wgrad_reduce":       # (ws, splits, dw, Co, Ci, Ci_real, KH, KW, transposed, beta)
-                    need = max(need, int(l.args[1]) * int(l.args[3]) * int(l.args[4]) * int(l.args[6]) * int(l.args[7]) * 4)
+                if l.name == "mi355_conv2d_wgrad_reduce":
+                    need = max(need, int(l.arg("splits")) * int(l.arg("Co")) * int(l.arg("Ci")) * int(l.arg("KH")) * int(l.arg("KW")) * 4)
             own = self._alloc(need, torch.uint8) if need else None
             if all(not isinstance(a, Ws) or (a.kind == "bytes" and own is not None) for l in tail for a in l.args):
                 for l in tail:

@@ -115,10 +115,10 @@ def test_maxpool_rides_in_the_batchnorm_apply_pass():
     net.engine.flatten()
     plan = net.engine.plan_for((2, 3, 64, 64), True, True, torch.bfloat16)
     names = [l.name for l in plan.fwd]
-    pooled = [l for l in plan.fwd if l.name == "mi355_bn_act_pool2" and l.args[6] is not None]
+    pooled = [l for l in plan.fwd if l.name == "mi355_bn_act_pool2" and l.arg("p") is not None]
     assert len(pooled) == 4 and "mi355_maxpool_fwd" not in names
     # (the other plain apply passes on even images run the same window-ordered kernel without a pooled output)
-    assert all(l.args[6] is None for l in plan.fwd if l.name == "mi355_bn_act_pool2" and l not in pooled) and "mi355_bn_act" not in names
+    assert all(l.arg("p") is None for l in plan.fwd if l.name == "mi355_bn_act_pool2" and l not in pooled) and "mi355_bn_act" not in names
     assert sum(a[0] == "pool" for a in plan.acts) == 4
     # ... and the pooling's gradient rides in the two BatchNorm backward passes of the layer that produced the pooled activation
     # (no mi355_maxpool_bwd pass over its gradient)
@@ -236,13 +236,13 @@ def test_recurrent_block_input_gradient_is_summed_once(monkeypatch):
     post4 = [l for l in on.bwd if l.name == "mi355_bn_bwd_apply_post4"]
     assert len(post4) == 18                                   # 9 RRCNN blocks x 2 recurrent blocks
     for l in post4:
-        ex = l.args[17:21]
+        ex = [l.arg(f"ex{i}") for i in range(4)]
         assert all(e is not None for e in ex) and len({id(e) for e in ex} | {id(l.args[0])}) == 5      # four earlier gradients + this one
-        assert all(e.ld == l.args[21] for e in ex) and l.args[14] is not None                          # one pitch; the operand's gradient
+        assert all(e.ld == l.arg("ldex") for e in ex) and l.arg("dpost") is not None                          # one pitch; the operand's gradient
     plain_on = [l for l in on.bwd if l.name == "mi355_bn_bwd_apply"]
     plain_off = [l for l in off.bwd if l.name == "mi355_bn_bwd_apply"]
     assert not any(l.name == "mi355_bn_bwd_apply_post4" for l in off.bwd)
-    with_post = lambda ls: sum(l.args[16] is not None for l in ls)                                       # dpost argument
+    with_post = lambda ls: sum(l.arg("dpost") is not None for l in ls)                                      # dpost argument
     assert with_post(plain_off) - with_post(plain_on) == 18 * 5 and len(plain_off) == len(plain_on) + 18
 
 
