@@ -351,6 +351,20 @@ int mi355_bce_logits(const float* z, const float* t, float* loss, float* dz, con
 /* CrossEntropyLoss(label_smoothing): loss[0], dz[B][C]. */
 int mi355_ce_smooth(const float* z, const int64_t* y, float* loss, float* dz, const float* gscale, int B,
                     int C, float smoothing, mi355_stream_t s);
+/* Cross-entropy against a DISTRIBUTION: two labels with a weight per sample (mixup / CutMix, utils/mix.py), label smoothing and
+ * optional per-class weights; mean reduction (nothing in the reference, which trains on hard labels).  z: [B][C] fp32 logits.
+ *   t[b][c]  = (1 - smoothing) * (lam[b] * [c == ya[b]] + (1 - lam[b]) * [c == yb[b]]) + smoothing / C
+ *   loss[0]  = (1 / B) * sum_b sum_c weight[c] * t[b][c] * (-log_softmax(z[b])[c])
+ *   dz[b][c] = (gscale[0] / B) * (softmax(z[b])[c] * sum_k (weight[k] * t[b][k]) - weight[c] * t[b][c])
+ * = torch.nn.functional.cross_entropy(z, t, weight=weight, label_smoothing=smoothing) with PROBABILITY targets: the sum is
+ * divided by B.  (With class-index targets and a weight torch divides by the sum of the picked weights instead; that
+ * normalisation is not built, so with a weight the hard-label case here differs from torch's class-index call by that factor.)
+ * yb and lam NULL together: hard labels, t = the smoothed one-hot of ya.  weight ([C]) NULL: all ones.  dz NULL: loss only;
+ * gscale NULL: 1.  Evaluated in double (inputs widened, exp / log in double, lam widened before 1 - lam) and rounded to float
+ * once on store; one workgroup, thread b % 256 owns row b, then a block fold in a fixed order: bit-reproducible.  Labels outside
+ * [0, C) are the caller's contract (they only select no class: nothing is indexed by them). */
+int mi355_ce_mix(const float* z, const int64_t* ya, const int64_t* yb, const float* lam, const float* weight, float* loss,
+                 float* dz, const float* gscale, int B, int C, float smoothing, mi355_stream_t s);
 /* Dice / BCE + Dice on fp32 logits and targets [B][per] (the reference's DiceLoss / CombinedLoss,
  * utils/clip_seg_finetuner.py:40-74).  p = sigmoid(z), I = sum p t, P = sum p, T = sum t, D = P + T + smooth:
  *   loss[0] = bce_weight * mean(BCEWithLogits(z, t)) + dice_weight * (1 - (2 I + smooth) / D)
@@ -592,6 +606,24 @@ int mi355_tta_fold(const float* z, int K, int N, int H, int W, const float* s2d,
  * kept / n_kept as in mi355_cls_decide (same order, same padding contract). */
 int mi355_cls_tta_decide(const float* logits, int K, int B, int C, int keep_class, float* probs, int32_t* pred, float* conf,
                          int32_t* agree, int32_t* kept, int32_t* n_kept, mi355_stream_t s);
+
+/* ---- batch mixing: mixup (Zhang et al. 2018) and CutMix (Yun et al. 2019) on the normalised batch (utils/mix.py; nothing in the
+ * reference) ------------------------------------------------------------------------------------------------------------- */
+/* x, out: fp32 [N][C][H][W], contiguous; perm: int32 [N], the partner of every sample; lam: fp32 [N]; box: int32 [N][4] =
+ * (y0, x0, y1, x1), half-open, 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W (empty: y0 == y1 or x0 == x1).  With a = x[n][c][i][j] and
+ * b = x[perm[n]][c][i][j]:
+ *   out[n][c][i][j] = b                                                   if y0 <= i < y1 and x0 <= j < x1
+ *                   = fl(fl(lam[n] * a) + fl(fl(1.0f - lam[n]) * b))      otherwise
+ * every operation rounded on its own (no FMA), nothing atomic: the same input gives the same bytes (tests/mix_ref.py restates it
+ * in numpy float32).  Mixup: an empty box.  CutMix: lam = 1, so outside the box out = fl(a + fl(0 * b)) = a for finite b (a = -0
+ * comes out as +0 where 0 * b = +0).  An unmixed sample: perm[n] = n.
+ * Out of place only (a sample is read as a by itself and as b by its partner): MI355_ERR_ARG, before the device is touched, for
+ * a null pointer, a non-positive size, N > 65535, C H W >= 2^31, or [x, x + N C H W) overlapping [out, out + N C H W).  perm
+ * entries in [0, N) and boxes within the image are the caller's contract (utils/mix.py checks both on the host, where they are
+ * drawn; the kernel reads an entry outside [0, N) as n, so a bad entry cannot read out of bounds).  16-byte accesses along W when W % 4 == 0 and x, out are 16-byte aligned, a scalar path otherwise; the box test is per
+ * element.  One pass: 2 N C H W floats read, N C H W written. */
+int mi355_mix_batch_f32(const float* x, const int32_t* perm, const float* lam, const int32_t* box, float* out, int N, int C, int H,
+                        int W, mi355_stream_t s);
 
 /* ---- Grad-CAM and image overlays (utils/explain.py; utils/pipeline.py process_images, reference pipeline.py:399-407) ---------- */
 /* dout[b][k] = (k == t_b) for the explained class t_b = target[b] when target is given (out of [0, K): a zero row, t_b = -1),

@@ -76,6 +76,54 @@ extern "C" int mi355_ce_smooth(const float* z, const int64_t* y, float* loss, fl
   return MI355_OK;
 }
 
+// ---- CrossEntropy against a distribution: two labels and a weight per sample (mixup / CutMix), smoothing, class weights ----------
+// t[c] = (1 - sm) (lam [c == ya] + (1 - lam) [c == yb]) + sm / C (header).  Everything in double, rounded to float once on store;
+// thread b % 256 owns row b, the block fold runs in a fixed order: bit-reproducible.  Labels only select (c == label), never index.
+__global__ __launch_bounds__(256) void ce_mix_kernel(const float* __restrict__ z, const int64_t* __restrict__ ya,
+                                                     const int64_t* __restrict__ yb, const float* __restrict__ lam,
+                                                     const float* __restrict__ weight, float* __restrict__ loss, float* __restrict__ dz,
+                                                     const float* __restrict__ gscale, int B, int C, float sm) {
+  const double gs = (gscale ? (double)gscale[0] : 1.0) / (double)B;
+  const double keep = 1.0 - (double)sm, uni = (double)sm / (double)C;
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const float* row = z + (size_t)b * C;
+    double mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmax(mx, (double)row[c]);
+    double se = 0.0;
+    for (int c = 0; c < C; ++c) se += exp((double)row[c] - mx);
+    const double lse = mx + log(se);
+    const int64_t la = ya[b], lb = yb ? yb[b] : la;
+    const double l = lam ? (double)lam[b] : 1.0, oml = 1.0 - l;
+    double wt_sum = 0.0, nll = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double wt = (weight ? (double)weight[c] : 1.0) * (keep * ((c == la ? l : 0.0) + (c == lb ? oml : 0.0)) + uni);
+      wt_sum += wt;
+      nll += wt * (lse - (double)row[c]);
+    }
+    acc += nll;
+    if (dz)
+      for (int c = 0; c < C; ++c) {
+        const double wt = (weight ? (double)weight[c] : 1.0) * (keep * ((c == la ? l : 0.0) + (c == lb ? oml : 0.0)) + uni);
+        dz[(size_t)b * C + c] = (float)(gs * (exp((double)row[c] - lse) * wt_sum - wt));
+      }
+  }
+  __shared__ double red[4];
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[0] = (float)((((red[0] + red[1]) + red[2]) + red[3]) / (double)B);
+}
+
+extern "C" int mi355_ce_mix(const float* z, const int64_t* ya, const int64_t* yb, const float* lam, const float* weight, float* loss,
+                            float* dz, const float* gscale, int B, int C, float smoothing, mi355_stream_t s) {
+  MI355_CHECK_ARG(z && ya && loss && B > 0 && C > 0, "ce_mix: bad arguments");
+  MI355_CHECK_ARG((yb == nullptr) == (lam == nullptr), "ce_mix: yb and lam go together");
+  hipLaunchKernelGGL(ce_mix_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, z, ya, yb, lam, weight, loss, dz, gscale, B, C, smoothing);
+  MI355_LAUNCH_CHECK();
+  return MI355_OK;
+}
+
 // ---- gradient norm + clip coefficient ------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, float* __restrict__ partial, long long n) {
   double acc = 0;

@@ -461,3 +461,86 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, out, target):
         return _CEFn.apply(out.float(), target, self.label_smoothing, getattr(out, "_mi355_plan", None))
+
+
+class _CEMixFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, ya, yb, lam, weight, smoothing, plan):
+        o = out.detach().contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=out.device)
+        lib.mi355_ce_mix(o, ya, yb, lam, weight, loss, None, None, o.shape[0], o.shape[1], float(smoothing))
+        ctx.o, ctx.t, ctx.plan, ctx.s = o, (ya, yb, lam, weight), plan, float(smoothing)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, plan = ctx.o, ctx.plan
+        ya, yb, lam, weight = ctx.t
+        n = o.numel()
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        scratch = torch.empty(1, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        lib.mi355_ce_mix(o, ya, yb, lam, weight, scratch, dz, gs, o.shape[0], o.shape[1], ctx.s)
+        return dz[:n].view(o.shape), None, None, None, None, None, None
+
+
+class MixCrossEntropyLoss(nn.Module):
+    """Cross-entropy against a distribution (mi355_ce_mix; mean reduction): ``target`` is an int64 label tensor [B] (hard labels) or a
+    ``utils.mix.MixedTarget`` — classes ``ya`` / ``yb`` with weights ``lam`` / ``1 - lam`` per sample, what mixup and CutMix produce —
+    with ``label_smoothing`` and optional per-class weights ``weight`` ([C]; kept as a float32 device buffer):
+
+        t = (1 - s) (lam onehot(ya) + (1 - lam) onehot(yb)) + s / C,   loss = (1 / B) sum_b sum_c weight_c t_bc (-log_softmax(z_b)_c)
+
+    = ``F.cross_entropy(z, t, weight=weight, label_smoothing=s)`` with PROBABILITY targets: the sum is divided by B.  With class-index
+    targets and a weight torch divides by the sum of the picked weights instead; that normalisation is not built, so the weighted
+    hard-label loss here differs from ``nn.CrossEntropyLoss(weight=w)(z, y)`` by that factor.  Without a weight the hard-label case is
+    ``CrossEntropyLoss(label_smoothing=s)``, evaluated in double.  One autograd node; the gradient goes straight into the plan's
+    ``dout`` when the logits come from a mi355 ``Net``.  Labels on the host are checked against [0, C); labels on the device only with
+    ``check_labels=True`` (one synchronisation per call) — the kernel never indexes by a label, one outside [0, C) selects no class."""
+
+    accepts_mixed_target = True
+
+    def __init__(self, label_smoothing=0.0, weight=None, check_labels=False):
+        super().__init__()
+        if not 0.0 <= label_smoothing <= 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1] ({label_smoothing})")
+        self.label_smoothing, self.check_labels = float(label_smoothing), bool(check_labels)
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).detach().reshape(-1).contiguous().clone()
+            if weight.numel() == 0 or not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+                raise ValueError(f"weight must hold finite values >= 0, one per class ({weight.tolist()})")
+        self.register_buffer("weight", weight)
+
+    def forward(self, out, target):
+        plan = getattr(out, "_mi355_plan", None)
+        out = out.float()
+        if out.dim() != 2:
+            raise ValueError(f"logits [B, C] expected, got {tuple(out.shape)}")
+        B, C = out.shape
+        if hasattr(target, "ya"):
+            ya, yb, lam = target.ya, target.yb, target.lam
+        else:
+            ya, yb, lam = target, None, None
+        labels = [ya] if yb is None else [ya, yb]
+        for t in labels:
+            if t.dim() != 1 or t.size(0) != B or t.dtype.is_floating_point:
+                raise ValueError(f"an integer label tensor [{B}] expected, got {t.dtype} {tuple(t.shape)}")
+            if (self.check_labels or not t.is_cuda) and (int(t.min()) < 0 or int(t.max()) >= C):
+                raise ValueError(f"labels must lie in [0, {C}), got {t.tolist()}")
+        dev = out.device
+        ya = ya.to(dev, torch.int64).contiguous()
+        if yb is not None:
+            if lam.shape != ya.shape:
+                raise ValueError(f"lam must hold one weight per sample, got {tuple(lam.shape)}")
+            yb, lam = yb.to(dev, torch.int64).contiguous(), lam.to(dev, torch.float32).contiguous()
+        w = self.weight
+        if w is not None:
+            if w.numel() != C:
+                raise ValueError(f"weight holds {w.numel()} classes, the logits {C}")
+            if w.device != dev:
+                self.weight = w = w.to(dev)
+        return _CEMixFn.apply(out, ya, yb, lam, w, self.label_smoothing, plan)
+
+    def extra_repr(self):
+        return f"label_smoothing={self.label_smoothing}, weight={None if self.weight is None else self.weight.tolist()}"

@@ -9,6 +9,11 @@ by device-side accumulation read back once per epoch, and model factories constr
 classes directly (the reference first tries a torch.hub download, helpers.py:158-166, which has
 no network here).
 
+Additions the reference does not have, all off by default: ``criterion=`` (a loss module of ``mi355.nn`` for the training and the
+validation loss) and a ``utils.mix.MixedBatches(train_dl, batch_mix)`` in the place of ``train_dl`` (the parameter list stays the
+reference's plus ``criterion``): mixup / CutMix of every training batch on the device by that ``utils.mix.BatchMix``; classifiers then
+train against a ``MixedTarget`` with ``mi355.nn.MixCrossEntropyLoss``, validation stays on hard labels and unmixed batches.
+
 Data parallel: when ``torch.distributed`` is initialised with more than one rank (``torchrun --nproc-per-node N
 utils/trainer.py ...``), ``train()`` shards the loaders' batches by rank (utils/distributed.py), wraps the model in
 ``mi355.dp.DataParallel`` (bucketed RCCL all-reduce of the flat gradient buffer overlapped with backward, 1/world folded
@@ -121,6 +126,20 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         model.engine._check_storage()                 # flat fp32 parameter / gradient buffers
     # criterion: a loss module of mi355.nn (mnn.DiceLoss(), mnn.CombinedLoss(), ...) for the training AND the validation loss;
     # None = the reference's choice
+    # train_dl may be a utils.mix.MixedBatches(loader, batch_mix): the loader is used as it would be without the wrapper and the
+    # utils.mix.BatchMix (mixup / CutMix) is applied to every TRAINING batch on the device; a plain loader = today's loop
+    batch_mix = None
+    if hasattr(train_dl, "batch_mix"):
+        train_dl, batch_mix = train_dl.loader, train_dl.batch_mix
+    if batch_mix is not None:
+        if bool(getattr(batch_mix, "seg", seg)) != bool(seg):
+            raise ValueError(f"batch_mix was built with seg={batch_mix.seg} but train() runs with seg={seg}")
+        if not seg:
+            if criterion is None:
+                criterion = mnn.MixCrossEntropyLoss(label_smoothing=0.1)
+            elif not getattr(criterion, "accepts_mixed_target", False):
+                raise TypeError(f"batch_mix turns the labels into a MixedTarget, which {type(criterion).__name__} cannot take: "
+                                "use mi355.nn.MixCrossEntropyLoss")
     if criterion is None:
         criterion = mnn.BCEWithLogitsLoss() if seg else mnn.CrossEntropyLoss(label_smoothing=0.1)
     STAGE1 = 5
@@ -182,6 +201,8 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         seen_all = 0                                  # samples this rank trained on (padding batches of the last step included)
         for x, y in train_dl:
             x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
+            if batch_mix is not None:
+                x, y = batch_mix(x, y)
             optimizer.zero_grad(set_to_none=True)
             out = model(x)
             if seg and out.dim() == 3:
@@ -195,7 +216,7 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
             loss_sum += loss.detach() * x.size(0)
             seen_all += x.size(0)
             if not seg:
-                hit_sum += (torch.argmax(out.detach(), 1) == y).sum()
+                hit_sum += (torch.argmax(out.detach(), 1) == (y if batch_mix is None else getattr(y, "hard", y))).sum()
                 seen += y.size(0)
 
         if dp is not None:

@@ -12,6 +12,8 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task seg --model attentionunet --seg-loss bce --lovasz-weight 0.5
     python utils/trainer.py --task seg --model attentionunet --data-root dataset --elastic-alpha 512 --elastic-sigma 20.5
     python utils/trainer.py --task seg --model attentionunet --data-root dataset --clahe-clip 4 --clahe-grid 8
+    python utils/trainer.py --task cls --model resnet18 --mixup-alpha 0.2 --cutmix-alpha 1.0 --class-weight balanced
+    python utils/trainer.py --task seg --model attentionunet --cutmix-alpha 1.0 --mix-prob 0.5
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -93,6 +95,16 @@ def build_parser():
                     help="--data-root: CLAHE (A.CLAHE) on the resized images of the train AND the validation transforms, clip limit; "
                          "0 = off; test and serve the model with the same values (tester.py --clahe-clip, JointPipeline.clahe)")
     ap.add_argument("--clahe-grid", type=int, default=8, help="CLAHE: tiles per side")
+    ap.add_argument("--mixup-alpha", type=float, default=0.0,
+                    help="cls: mixup (Zhang et al. 2018) on the training batches, lam ~ Beta(alpha, alpha); 0 = off; usual value 0.2")
+    ap.add_argument("--cutmix-alpha", type=float, default=0.0,
+                    help="cls and seg: CutMix (Yun et al. 2019) on the training batches (seg: image and mask get the same box); 0 = off; "
+                         "usual value 1.0")
+    ap.add_argument("--mix-prob", type=float, default=1.0, help="mixup / CutMix: probability that a batch (or a sample) is mixed")
+    ap.add_argument("--mix-switch-prob", type=float, default=0.5, help="both alphas > 0: probability of CutMix, else mixup")
+    ap.add_argument("--mix-per-sample", action="store_true", help="mixup / CutMix: a draw per sample (default: one per batch)")
+    ap.add_argument("--class-weight", choices=["none", "balanced"], default="none",
+                    help="cls: per-class loss weights n / (C * count_c) from the training files (--data-root; ignored for synthetic data)")
     return ap
 
 
@@ -118,6 +130,52 @@ def clahe_arg(args):
     clip, grid = check_clahe(args.clahe_clip, args.clahe_grid)
     tile_geometry(args.size, args.size, *grid)
     return clip, grid
+
+
+def mix_arg(args, task, rank=0):
+    """The mixer of one task's training batches (train() takes it as utils.mix.MixedBatches(train_dl, mixer)): None with both alphas 0
+    (today's loop), else a utils.mix.BatchMix seeded with the rank (data-parallel ranks draw different mixes), validated here so that
+    a bad flag fails before any data is read.  For --task seg only --cutmix-alpha is accepted."""
+    for flag, v in (("--mixup-alpha", args.mixup_alpha), ("--cutmix-alpha", args.cutmix_alpha)):
+        if not v >= 0 or v == float("inf"):
+            raise ValueError(f"{flag} must be a finite number >= 0 ({v})")
+    for flag, v in (("--mix-prob", args.mix_prob), ("--mix-switch-prob", args.mix_switch_prob)):
+        if not 0 <= v <= 1:
+            raise ValueError(f"{flag} must lie in [0, 1] ({v})")
+    if task == "seg" and args.mixup_alpha > 0:
+        if args.task == "both":
+            raise ValueError("--mixup-alpha is for classifiers only: with --task both run the two tasks separately")
+        raise ValueError("--mixup-alpha is not accepted with --task seg (a blended mask breaks the thresholded losses); use --cutmix-alpha")
+    if args.mixup_alpha == 0 and args.cutmix_alpha == 0:
+        return None
+    from utils.mix import BatchMix
+    return BatchMix(args.mixup_alpha, args.cutmix_alpha, p=args.mix_prob, switch_p=args.mix_switch_prob, per_sample=args.mix_per_sample,
+                    seed=int(rank), seg=task == "seg")
+
+
+def balanced_class_weights(labels, n_classes):
+    """n / (C * count_c) per class (sklearn's "balanced"); a class without samples gets 0 (it cannot occur as a label)"""
+    count = [0] * n_classes
+    for c in labels:
+        count[int(c)] += 1
+    n = sum(count)
+    return [n / (n_classes * k) if k else 0.0 for k in count]
+
+
+def cls_criterion(args, batch_mix, dataset=None, indices=None, say=print):
+    """The classifier's loss: None = train()'s own default (CrossEntropyLoss(0.1), or MixCrossEntropyLoss(0.1) on mixed batches);
+    with --class-weight balanced MixCrossEntropyLoss(0.1, weight) from the labels of ``dataset.samples`` at ``indices``."""
+    if args.class_weight == "none":
+        return None
+    if dataset is None or not hasattr(dataset, "samples"):
+        say("--class-weight balanced needs the file list of --data-root: ignored for synthetic data")
+        return None
+    from mi355 import nn as mnn
+    from utils.helpers import CLASSES
+    idx = range(len(dataset.samples)) if indices is None else indices
+    w = balanced_class_weights([dataset.samples[i][1] for i in idx], len(CLASSES))
+    say(f"class weights (balanced): {', '.join(f'{c} {v:.3f}' for c, v in zip(CLASSES, w))}")
+    return mnn.MixCrossEntropyLoss(label_smoothing=0.1, weight=w)
 
 
 def seg_criterion(args):
@@ -179,7 +237,9 @@ def main():
         split_gen = torch.Generator().manual_seed(seed[0])
     say = print if rank == 0 else (lambda *a, **k: None)
     results = {}
-    for task in (["cls", "seg"] if args.task == "both" else [args.task]):
+    tasks = ["cls", "seg"] if args.task == "both" else [args.task]
+    mixes = {task: mix_arg(args, task, rank) for task in tasks}          # (a bad flag fails before any data is read)
+    for task in tasks:
         names = [args.model] if args.model else (CLS_MODELS if task == "cls" else SEG_MODELS)
         bs = 16 if task == "cls" else 8
         if args.data_root:
@@ -201,12 +261,18 @@ def main():
             tr, va = random_split(full, [n_train, len(full) - n_train], generator=split_gen) if split_gen is not None else \
                 random_split(full, [n_train, len(full) - n_train])
             train_dl, val_dl = make_loader(tr, bs, True), make_loader(va, bs, False)
+        if mixes[task] is not None:
+            from utils.mix import MixedBatches
+            train_dl = MixedBatches(train_dl, mixes[task])
+        cls_crit = None
+        if task == "cls":
+            cls_crit = cls_criterion(args, mixes[task], ds_tr if args.data_root else None, perm[:n_train] if args.data_root else None, say)
         for name in names:
             say(f"\n{'=' * 20} {task.upper()} :: {name} {'=' * 20}")
             if task == "cls":
                 model, head = get_class_model(name)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "classification_models"),
-                             seg=False, cls_head_name=head)
+                             seg=False, cls_head_name=head, criterion=cls_crit)
             else:
                 model = get_seg_model(name)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True,
