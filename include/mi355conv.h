@@ -607,6 +607,33 @@ int mi355_tta_fold(const float* z, int K, int N, int H, int W, const float* s2d,
 int mi355_cls_tta_decide(const float* logits, int K, int B, int C, int keep_class, float* probs, int32_t* pred, float* conf,
                          int32_t* agree, int32_t* kept, int32_t* n_kept, mi355_stream_t s);
 
+/* ---- sliding-window inference (utils/sliding.py; nothing in the reference).  A batch kept at a higher resolution is cut into
+ * overlapping T x T tiles on a grid of Py row starts ys[] and Px column starts xs[]: tile p = iy * Px + ix of sample n has its
+ * top-left corner at (ys[iy], xs[ix]).  ys and xs are HOST pointers (int32, 1 <= Py, Px <= 64): the launcher validates them
+ * (strictly ascending, ys[0] == 0, ys[Py - 1] == H - T, every gap <= T so that no pixel is uncovered; likewise xs against W) and
+ * passes them to the kernel by value; everything else is device memory.  In both kernels every fp32 operation is rounded on its
+ * own (no FMA), nothing is atomic and every sum runs in a fixed order: outputs are bit-identical run to run (tests/sliding_ref.py
+ * restates them in numpy float32).  T < 1, T > H, T > W, M < 1, N < 1, a NULL required pointer or invalid starts: an error from
+ * the launcher, nothing is launched.  So is a grid on which more than 255 tiles cover one pixel (the most starts within T pixels
+ * along y times the same along x; cover is a uint8 plane): utils/sliding.py's grids, overlap <= 0.75, stay at 7 x 7 = 49. ---- */
+/* dst[i][c][ty][tx] = src[n][c][ys[iy] + ty][xs[ix] + tx], tiles[i] = (n * Py + iy) * Px + ix  (device int32 [M]; entries may repeat:
+ * the caller pads the last chunk by repeating a tile; an entry outside [0, N Py Px) leaves dst[i] alone).  src fp32 [N][C][H][W],
+ * dst fp32 [M][C][T][T], src != dst. */
+int mi355_tile_gather_f32(const float* src, int N, int C, int H, int W, int T, const int32_t* ys, int Py, const int32_t* xs, int Px,
+                          const int32_t* tiles, int M, float* dst, mi355_stream_t s);
+/* z: fp32 [N * Py * Px][T][T], the one-channel logit maps of the tiles; wy, wx: device fp32 [T], all > 0 (caller's contract).
+ * For pixel (y, x) of sample n, over the tiles that cover it, iy ascending and within iy ix ascending, from num = den = 0,
+ * lo = +inf, hi = -inf, cnt = 0:
+ *   v = z[(n Py + iy) Px + ix][y - ys[iy]][x - xs[ix]];  if (prob) v = sigmoid(v)   (mi355_mask_scatter's expression)
+ *   w = wy[y - ys[iy]] * wx[x - xs[ix]];  num = num + (w * v);  den = den + w;  lo = min(lo, v);  hi = max(hi, v);  cnt++
+ *   mean[n][y][x] = num / den;  spread[n][y][x] = hi - lo;  cover[y][x] = cnt (uint8 [H][W], the same for every n)
+ *   mask[idx ? idx[n] : n][y][x] = 255 where mean > thr (prob) or sigmoid(mean) > thr (otherwise), else 0
+ * spread, cover, mask, idx may be NULL (skipped; idx: rows in place).  One tile with wy = wx = 1 and prob = 0: mean has z's bits
+ * — except that z = -0 comes out as +0 (num = 0 + (1 * -0) = +0) — and mask has mi355_mask_scatter's bytes.  N <= 65535. */
+int mi355_tile_blend(const float* z, int N, int H, int W, int T, const int32_t* ys, int Py, const int32_t* xs, int Px,
+                     const float* wy, const float* wx, int prob, float thr, const int32_t* idx, float* mean, float* spread,
+                     uint8_t* cover, uint8_t* mask, mi355_stream_t s);
+
 /* ---- batch mixing: mixup (Zhang et al. 2018) and CutMix (Yun et al. 2019) on the normalised batch (utils/mix.py; nothing in the
  * reference) ------------------------------------------------------------------------------------------------------------- */
 /* x, out: fp32 [N][C][H][W], contiguous; perm: int32 [N], the partner of every sample; lam: fp32 [N]; box: int32 [N][4] =

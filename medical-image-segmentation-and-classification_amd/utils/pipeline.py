@@ -15,7 +15,10 @@ the masks by connected components on the device before they are overlaid and add
 ``pipeline.clahe = (clip, grid)`` equalises the resized images in ``process_files`` / ``process_images`` (utils/clahe.py) — the
 values the models were trained with (trainer.py --clahe-clip / --clahe-grid); the overlays are still drawn on the file's own pixels.
 ``tta`` (a preset name or a list of views, utils/tta.py): both models predict on every view and the merged predictions decide; the
-result gains a per-pixel uncertainty map and the views' agreement, and the analysis text says how stable the highlighted area is."""
+result gains a per-pixel uncertainty map and the views' agreement, and the analysis text says how stable the highlighted area is.
+``sliding=(tile, overlap, weighting)`` (utils/sliding.py): the kept samples are segmented at the resolution of ``predict``'s ``x_seg``
+(``seg_size`` in ``process_files`` / ``process_images``) by overlapping windows of ``tile`` pixels blended on the GPU; the masks come
+back at that resolution, with a map of how far overlapping windows disagree.  The classifier's path is unchanged."""
 from __future__ import annotations
 
 import torch
@@ -26,13 +29,15 @@ CLASSES = ["COVID", "Healthy", "Non-COVID"]          # pipeline.py:22
 
 
 class _KeywordOptions(type):
-    """``JointPipeline(..., tta=None, tta_merge="prob")``: the two options are keywords of the call, set through their properties once
-    ``__init__`` has run, so ``__init__`` keeps the positional parameter list its callers rely on."""
+    """``JointPipeline(..., tta=None, tta_merge="prob", sliding=None, seg_size=None)``: the options are keywords of the call, set
+    through their properties once ``__init__`` has run, so ``__init__`` keeps the positional parameter list its callers rely on."""
 
-    def __call__(cls, *args, tta=None, tta_merge="prob", **kwargs):
+    def __call__(cls, *args, tta=None, tta_merge="prob", sliding=None, seg_size=None, **kwargs):
         self = super().__call__(*args, **kwargs)
         self.tta_merge = tta_merge
         self.tta = tta
+        self.sliding = sliding
+        self.seg_size = seg_size
         return self
 
 
@@ -40,6 +45,7 @@ class JointPipeline(metaclass=_KeywordOptions):
     def __init__(self, classification_model, segmentation_model, device="cuda", classes=CLASSES, positive="COVID", bucket=4, postprocess=None):
         self.device = torch.device(device)
         self._tta, self._tta_merge = None, "prob"
+        self._sliding, self._seg_size, self._sw = None, None, None
         self.classes = list(classes)
         self.keep = self.classes.index(positive)
         self.bucket = int(bucket)
@@ -76,7 +82,41 @@ class JointPipeline(metaclass=_KeywordOptions):
             self._tta = None
             return
         from utils.tta import check_views
+        if self._sliding is not None:
+            raise ValueError("JointPipeline: tta together with sliding is not supported: set one of the two")
         self._tta = check_views(value)
+
+    @property
+    def sliding(self):
+        """None (default: the segmenter sees the batch ``predict`` is given) or (tile, overlap, weighting): sliding-window
+        segmentation (utils/sliding.py), validated on assignment.  Not together with ``tta``."""
+        return self._sliding
+
+    @sliding.setter
+    def sliding(self, value):
+        if value is None:
+            self._sliding = None
+            return
+        from utils.sliding import check_sliding
+        value = check_sliding(value)
+        if self._tta is not None:
+            raise ValueError("JointPipeline: sliding together with tta is not supported: set one of the two")
+        self._sliding = value
+
+    @property
+    def seg_size(self):
+        """None (default) or the side ``process_files`` / ``process_images`` resize the images to for the sliding-window segmenter
+        (the classifier keeps ``size``); at least the tile, checked when used together with ``sliding``."""
+        return self._seg_size
+
+    @seg_size.setter
+    def seg_size(self, value):
+        if value is None:
+            self._seg_size = None
+            return
+        if isinstance(value, bool) or int(value) != value or int(value) < 1:
+            raise ValueError(f"seg_size must be None or a positive integer, got {value!r}")
+        self._seg_size = int(value)
 
     @property
     def tta_merge(self):
@@ -91,7 +131,7 @@ class JointPipeline(metaclass=_KeywordOptions):
         self._tta_merge = value
 
     @torch.no_grad()
-    def predict(self, x, explain=False):
+    def predict(self, x, explain=False, x_seg=None):
         """x: [B,3,H,W] normalised float (B <= 1024).  Returns a dict of device tensors:
         ``pred`` int32 [B] class index, ``confidence`` float [B] in percent, ``masks`` uint8 [B,H,W] (0 / 255; all zero
         where no segmentation ran), ``segmented`` bool [B].  ``explain``: also ``cam`` float32 [B,H,W] (and ``cam_lowres`` at
@@ -102,9 +142,23 @@ class JointPipeline(metaclass=_KeywordOptions):
         ``pred`` / ``confidence`` come from the views' mean softmax and the masks from their merged maps (before any postprocess);
         also ``agreement`` int32 [B] (views whose own class is ``pred``), ``uncertainty`` fp32 [B,H,W] (the variance of the views'
         probabilities, or logits for tta_merge="logit"; zero where nothing was segmented) and ``stable_percent`` fp32 [B] (the share
-        of the pixels of ``masks`` — the cleaned masks with a postprocess — on which every view that sees them votes alike; 0 without a mask).  ``explain`` with ``tta``: ValueError."""
+        of the pixels of ``masks`` — the cleaned masks with a postprocess — on which every view that sees them votes alike; 0 without a mask).  ``explain`` with ``tta``: ValueError.
+        With ``sliding``: the kept samples are taken from ``x_seg`` ([B,3,Hs,Ws], the same images at the segmenter's resolution;
+        default x; Hs, Ws >= tile) and segmented window by window in chunks of ``bucket`` windows; ``masks`` are uint8 [B,Hs,Ws] and
+        ``seam_spread`` fp32 [B,Hs,Ws] is, per pixel, the largest minus the smallest logit the windows covering it give (zero where
+        one window covers and where nothing was segmented).  ``x_seg`` without ``sliding``: ValueError."""
         x = x.to(self.device, dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
+        if x_seg is not None and self.sliding is None:
+            raise ValueError("JointPipeline: x_seg is the sliding-window segmenter's input: set sliding=(tile, overlap, weighting)")
+        seam = None
+        if self.sliding is not None:
+            x_seg = x if x_seg is None else x_seg.to(self.device, dtype=torch.float32).contiguous()
+            if x_seg.dim() != 4 or x_seg.shape[0] != B or x_seg.shape[1] != 3:
+                raise ValueError(f"JointPipeline: x_seg must be [{B},3,Hs,Ws], got {tuple(x_seg.shape)}")
+            H, W = x_seg.shape[2:]                    # the masks' size from here on
+            if min(H, W) < self.sliding[0]:
+                raise ValueError(f"JointPipeline: sliding: the segmenter's input ({H} x {W}) must be at least the tile ({self.sliding[0]})")
         if self.tta is not None:
             if explain:
                 raise ValueError("JointPipeline: explain=True is not defined with tta (Grad-CAM of an averaged prediction)")
@@ -124,7 +178,14 @@ class JointPipeline(metaclass=_KeywordOptions):
         masks = torch.zeros(B, H, W, dtype=torch.uint8, device=self.device)
         segmented = pred == self.keep
         n = int(n_kept)                               # the one host sync: sizes the segmentation launch
-        if n and self.segmentation_model is not None:
+        if self.sliding is not None:
+            seam = torch.zeros(B, H, W, dtype=torch.float32, device=self.device)
+        if n and self.segmentation_model is not None and self.sliding is not None:
+            xs = torch.empty(n, 3, H, W, dtype=torch.float32, device=self.device)
+            lib.mi355_gather_rows(x_seg, kept, n, 3 * H * W, xs)
+            f = self._window_segmenter()(xs, kept, masks)
+            seam[kept[:n].long()] = f["spread"]
+        elif n and self.segmentation_model is not None:
             npad = -(-n // self.bucket) * self.bucket
             if npad > n:
                 kept[n:npad] = kept[0]                 # padding rows repeat a kept sample; their output is dropped
@@ -137,6 +198,8 @@ class JointPipeline(metaclass=_KeywordOptions):
         elif self.segmentation_model is None:
             segmented = torch.zeros_like(segmented)
         out = {"pred": pred, "confidence": conf, "masks": masks, "segmented": segmented}
+        if seam is not None:
+            out["seam_spread"] = seam
         if self.postprocess is not None:
             clean = self.postprocess(masks)            # 0 / 255 against 0.5; rows without a segmentation are empty and stay so
             out.update(masks=clean["mask"], masks_raw=masks, n_lesions=clean["n_kept"], area_percent=clean["area_percent"],
@@ -144,6 +207,16 @@ class JointPipeline(metaclass=_KeywordOptions):
         if cams is not None:
             out["cam"], out["cam_lowres"] = cams["cam"], cams["cam_lowres"]
         return out
+
+    def _window_segmenter(self):
+        """the SlidingWindowSegmenter of the current (sliding, bucket, segmentation_model), kept between calls: it holds the tile
+        lists and the window weights on the device"""
+        from utils.sliding import SlidingWindowSegmenter
+        key = (self.sliding, self.bucket, self.segmentation_model)
+        if self._sw is None or self._sw[0] != key[:2] or self._sw[1] is not key[2]:
+            tile, overlap, weighting = self.sliding
+            self._sw = (key[:2], key[2], SlidingWindowSegmenter(key[2], tile, overlap, weighting, "logit", 0.5, self.bucket))
+        return self._sw[2]
 
     def _predict_tta(self, x):
         """predict() with test-time augmentation: the same steps, every model call replaced by its K views and their merge"""
@@ -187,12 +260,28 @@ class JointPipeline(metaclass=_KeywordOptions):
         from utils.dataset import decode_batch, read_files
         from utils.gpu_transforms import SegBatchTransform
         imgs = decode_batch(read_files(paths), 3, threads, names=list(paths))
-        x = SegBatchTransform(size, train=False, device=self.device, clahe=self.clahe)(imgs.to(self.device, non_blocking=True))
-        return self.process_batch(x)
+        imgs = imgs.to(self.device, non_blocking=True)
+        x = SegBatchTransform(size, train=False, device=self.device, clahe=self.clahe)(imgs)
+        return self.process_batch(x, self._seg_input(imgs, size))
 
-    def process_batch(self, x):
-        """The reference's per-image result shape: list of (prediction, confidence_percent, mask uint8 [H,W] or None)."""
-        r = self.predict(x)
+    def _seg_input(self, imgs, size):
+        """the decoded images resized to ``seg_size`` by the same transform (same CLAHE), or None: the segmenter sees the
+        classifier's batch"""
+        if self.seg_size is None:
+            return None
+        if self.sliding is None:
+            raise ValueError("JointPipeline: seg_size is the sliding-window segmenter's input size: set sliding=(tile, overlap, weighting)")
+        if self.seg_size < self.sliding[0]:
+            raise ValueError(f"JointPipeline: seg_size ({self.seg_size}) must be at least the tile ({self.sliding[0]})")
+        from utils.gpu_transforms import SegBatchTransform
+        if self.seg_size == size:
+            return None
+        return SegBatchTransform(self.seg_size, train=False, device=self.device, clahe=self.clahe)(imgs)
+
+    def process_batch(self, x, x_seg=None):
+        """The reference's per-image result shape: list of (prediction, confidence_percent, mask uint8 [H,W] or None).  ``x_seg``:
+        predict's."""
+        r = self.predict(x, x_seg=x_seg)
         pred, conf, seg = r["pred"].cpu(), r["confidence"].cpu(), r["segmented"].cpu()
         masks = r["masks"].cpu()
         return [(self.classes[int(pred[i])], float(conf[i]), masks[i] if bool(seg[i]) else None) for i in range(len(pred))]
@@ -212,13 +301,22 @@ class JointPipeline(metaclass=_KeywordOptions):
         for i, b in enumerate(bufs):
             groups.setdefault(png_size(b), []).append(i)
         tf = SegBatchTransform(size, train=False, device=self.device, clahe=self.clahe)
-        order, imgs, xs = [], [], []
+        order, imgs, xs, xsegs = [], [], [], []
         for idx in groups.values():
             im = decode_batch([bufs[i] for i in idx], 3, threads, names=[paths[i] for i in idx]).to(self.device, non_blocking=True)
             order.append(idx)
             imgs.append(im)
             xs.append(tf(im))
-        r = self.predict(torch.cat(xs) if len(xs) > 1 else xs[0], explain=explain)
+            xsegs.append(self._seg_input(im, size))
+        x_seg = None if xsegs[0] is None else (torch.cat(xsegs) if len(xsegs) > 1 else xsegs[0])
+        r = self.predict(torch.cat(xs) if len(xs) > 1 else xs[0], explain=explain, x_seg=x_seg)
+        grid_line = None
+        if self.sliding is not None:
+            from utils.sliding import tile_starts
+            Hs, Ws = r["masks"].shape[1:]
+            tile, overlap, weighting = self.sliding
+            grid_line = (f"\nSliding window: {len(tile_starts(Hs, tile, overlap))} x {len(tile_starts(Ws, tile, overlap))} tiles of {tile} px "
+                         f"on {Hs} x {Ws} (overlap {overlap:g}, {weighting} weights).")
         pred, conf = r["pred"].cpu(), r["confidence"].cpu()
         lesions = (r["n_lesions"].cpu(), r["area_percent"].cpu()) if "n_lesions" in r else None
         stable = r["stable_percent"].cpu() if "stable_percent" in r else None
@@ -243,6 +341,8 @@ class JointPipeline(metaclass=_KeywordOptions):
                     text += "\nInfection areas have been highlighted in red (segmentation model)."
                     if lesions is not None:
                         text += f"\nLesions: {int(lesions[0][row + j])} (area {float(lesions[1][row + j]):.2f}% of the image)."
+                    if grid_line is not None:
+                        text += grid_line
                     if stable is not None:
                         text += (f"\nStable under test-time augmentation: {float(stable[row + j]):.2f}% of the highlighted pixels "
                                  f"({len(self.tta)} views).")

@@ -270,14 +270,24 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
     ``auc_samples`` of them: an image without a positive pixel (or without a negative one) has no ROC-AUC and is counted out.  The LOGITS
     are ranked: the sigmoid is monotone, so the order, the ties that matter and with them every figure are those of the probabilities
     in exact arithmetic, and nothing passes through expf.  With test-time augmentation the merged map is ranked — with
-    ``merge="prob"`` the merged probabilities."""
+    ``merge="prob"`` the merged probabilities.
+    Sliding-window inference: pass ``utils.sliding.SlidingWindowSegmenter(model, tile, overlap, weighting, merge)`` as the model (the
+    loader's images are then larger than the tile).  Every metric is taken from the windows' blended map, and the result gains
+    ``sw_tiles`` (windows per image) and ``sw_seam_spread`` (per sample the mean, over the pixels more than one window covers, of the
+    largest minus the smallest value the windows give the pixel — logits, or probabilities for ``merge="prob"``; 0 for a sample
+    without such pixels; averaged over the samples)."""
+    from utils.sliding import SlidingWindowSegmenter
     from utils.tta import TTASegmenter
     model.eval()
     tta = seg_tta = model if isinstance(model, TTASegmenter) else None
+    sw = model if isinstance(model, SlidingWindowSegmenter) else None
     is_logit = True                               # the model's output; with tta the merged map, a probability unless merge="logit"
     if tta is not None:
         tta_merge = seg_tta.merge
         is_logit = tta_merge == "logit"
+    if sw is not None:
+        is_logit = sw.merge == "logit"
+    seam, sw_tiles = [], 0
     tot = {k: 0.0 for k in ("iou", "dice", "pixel_accuracy", "precision", "recall", "f1")}
     n = 0
     print(f"\n{'=' * 60}\nTesting Segmentation Model: {model_name}\n{'=' * 60}")
@@ -286,7 +296,14 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
         from utils.ranking import rank_metrics
     with torch.no_grad():
         for images, masks in test_loader:
-            if tta is None:
+            if sw is not None:
+                r = sw(images.to(device))
+                out = r["mean"]
+                over = r["cover"] > 1
+                seam.append((r["spread"].double() * over).flatten(1).sum(1) / over.sum().clamp(min=1))
+                gy, gx = sw.grid(images.shape[-2], images.shape[-1])
+                sw_tiles = len(gy) * len(gx)
+            elif tta is None:
                 out = model(images.to(device))
             else:
                 r = seg_tta(images.to(device))
@@ -305,6 +322,8 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
     surf = []
     if tta is not None:                           # read back with the counters below
         unanimous = torch.cat(unanimous).cpu().numpy()
+    if sw is not None:
+        seam = torch.cat(seam).cpu().numpy()
     for cnt, per, raw in pending:                 # single read-back after the loop
         for c in cnt.double().cpu().numpy():
             m = _metrics_from_counts(c, per)
@@ -326,6 +345,9 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
     if tta is not None:
         avg["tta_unanimous"] = float(unanimous.mean()) * 100
         avg["tta_views"] = len(seg_tta.views)
+    if sw is not None:
+        avg["sw_tiles"] = int(sw_tiles)
+        avg["sw_seam_spread"] = float(seam.mean())
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
     print(f"IoU (Jaccard):     {avg['iou']:.2f}%\nDice Coefficient:  {avg['dice']:.2f}%\nPixel Accuracy:    {avg['pixel_accuracy']:.2f}%")
     print(f"Precision:         {avg['precision']:.2f}%\nRecall:            {avg['recall']:.2f}%\nF1 Score:          {avg['f1']:.2f}%"
@@ -333,6 +355,8 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
              f"Surface Dice @2px: {avg['surface_dice']:.2f}% ({avg['surface_samples']} of {n} samples)" if surface else "")
           + (f"\nPixel AUROC / AP:  {avg['pixel_auroc']:.4f} / {avg['pixel_ap']:.4f} ({avg['auc_samples']} of {n} samples)" if auc else "")
           + (f"\nTTA unanimous:     {avg['tta_unanimous']:.2f}% of the pixels ({avg['tta_views']} views, merged {tta_merge})" if tta is not None else "")
+          + (f"\nSliding window:    {avg['sw_tiles']} tiles of {sw.tile} px per image (overlap {sw.overlap:g}, {sw.weighting} weights, merged "
+             f"{sw.merge}), seam spread {avg['sw_seam_spread']:.4f}" if sw is not None else "")
           + f"\n{'=' * 60}\n")
     return avg
 
@@ -345,7 +369,8 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", auc=False, calibration_bins=15, surface=False):
+                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, auc=False, calibration_bins=15,
+                    surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -358,8 +383,21 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     ``tta_merge``: test-time augmentation for every model (test_classification_model(tta=...); the segmenters are handed to
     test_segmentation_model wrapped in utils.tta.TTASegmenter).  ``auc`` / ``calibration_bins``: ROC-AUC, average precision and
     calibration for every classifier (test_classification_model(auc=True)), per-image pixel ROC-AUC and average precision for every
-    segmenter (evaluate_segmentation_model(auc=True))."""
+    segmenter (evaluate_segmentation_model(auc=True)).  ``sliding=(tile, overlap, weighting)``: the segmenters are handed on wrapped in
+    utils.sliding.SlidingWindowSegmenter (windows of ``tile`` pixels blended on the GPU; the classifiers are untouched), and ``size``
+    (default IMG_SIZE, at least ``tile``) is the side the default SEGMENTATION loader resizes to (the classifiers keep IMG_SIZE) — the
+    point of the option is a ``size`` above the training size with ``tile`` at the training size.  ``sliding`` together with ``tta``: ValueError."""
     from utils.helpers import get_class_model, get_seg_model
+    size = IMG_SIZE if size is None else int(size)
+    if size < 1:
+        raise ValueError(f"size >= 1 required, got {size}")
+    if sliding is not None:
+        from utils.sliding import check_sliding
+        if tta is not None:
+            raise ValueError("sliding together with tta is not supported: pass one of the two")
+        sliding = check_sliding(sliding)
+        if size < sliding[0]:
+            raise ValueError(f"sliding: size must be at least the tile ({sliding[0]}), got {size}")
     if tta is not None:
         from utils.tta import MERGES, check_views
         tta = check_views(tta)
@@ -403,7 +441,7 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             from utils.dataset import ClassificationDataset, GpuBatchLoader, SegmentationDataset
             from utils.gpu_transforms import ClsBatchTransform, SegBatchTransform
             if seg:
-                ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(IMG_SIZE, train=False, device=device, clahe=clahe), split="test")
+                ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(size, train=False, device=device, clahe=clahe), split="test")
                 return GpuBatchLoader(ds, max(1, batch_size // 2), shuffle=False, device=device)
             ds = ClassificationDataset(DATA_ROOT, ClsBatchTransform(IMG_SIZE, train=False, device=device, clahe=clahe), split="test")
             return GpuBatchLoader(ds, batch_size, shuffle=False, device=device)
@@ -435,6 +473,11 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         if auc:
             wrap = (lambda m: TTASegmenter(m, tta, tta_merge)) if tta is not None else (lambda m: m)
             seg_test = lambda m, l, d, name: evaluate_segmentation_model(wrap(m), l, d, name, surface=surface, auc=True)  # noqa: E731
+        if sliding is not None:                          # (tta is None here)
+            from utils.sliding import SlidingWindowSegmenter
+            sw_batch = max(1, batch_size // 2)
+            sw_wrap = lambda m: SlidingWindowSegmenter(m, sliding[0], sliding[1], sliding[2], batch=sw_batch)  # noqa: E731
+            seg_test = lambda m, l, d, name: evaluate_segmentation_model(sw_wrap(m), l, d, name, surface=surface, auc=auc)  # noqa: E731
         run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
     return results
 
@@ -544,6 +587,11 @@ def build_parser():
     _ap.add_argument("--tta", choices=("hflip", "rot", "full"), default=None,
                      help="test-time augmentation: predict on these views and score the merged prediction (utils/tta.py)")
     _ap.add_argument("--tta-merge", choices=("prob", "logit"), default="prob", help="TTA: average the probabilities or the logits")
+    _ap.add_argument("--sw-tile", type=int, default=0,
+                     help="sliding-window inference for the segmenters: the window side (the training size); 0 = off (utils/sliding.py)")
+    _ap.add_argument("--sw-overlap", type=float, default=0.5, help="sliding window: the share of a window its neighbour overlaps (0 .. 0.75)")
+    _ap.add_argument("--sw-weight", choices=("gaussian", "constant"), default="gaussian", help="sliding window: how overlapping windows are weighted")
+    _ap.add_argument("--size", type=int, default=IMG_SIZE, help="the side the segmentation test images are resized to (with --sw-tile: at least the tile)")
     _ap.add_argument("--auc", action="store_true",
                      help="also report ROC-AUC and average precision (per class / per image over the pixels) and the classifiers' ECE, Brier score and NLL")
     _ap.add_argument("--calibration-bins", type=int, default=15, help="--auc: confidence bins of the expected calibration error")
@@ -565,6 +613,12 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
         _kw.update(tta=_args.tta, tta_merge=_args.tta_merge)
     if _args.auc:
         _kw.update(auc=True, calibration_bins=_args.calibration_bins)
+    if _args.sw_tile != 0:
+        if _args.tta is not None:
+            raise ValueError("--tta together with --sw-tile is not supported: pass one of the two")
+        _kw.update(sliding=(_args.sw_tile, _args.sw_overlap, _args.sw_weight))
+    if _args.size != IMG_SIZE:
+        _kw["size"] = _args.size
     results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
     save_results_to_csv(results, cls_output_path="classification_test_results.csv", seg_output_path="segmentation_test_results.csv")
