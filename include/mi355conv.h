@@ -477,6 +477,61 @@ int mi355_cls_calibration_ws_ints(int N, int C, int bins);
 int mi355_cls_calibration(const float* x, int N, int C, int is_prob, const int32_t* labels, int bins, int32_t* ws,
                           long long ws_ints, int64_t* bin_count, int64_t* bin_correct, double* bin_conf, double* out,
                           float* scores_t, mi355_stream_t s);
+/* Resampling statistics (nothing in the reference): bootstrap weights, the evaluation figures on the resampled multiset,
+ * percentile intervals over the replicates and DeLong's components.  A resample is a row of int32 weights, never a copy of
+ * the data: counts int32 [R1][n], R1 = R + 1, counts[r][i] = how often replicate r drew sample i.  ROW 0 IS THE IDENTITY
+ * (every weight 1), so row 0 of every output below is the point estimate, computed by the same code.  Weights a caller
+ * supplies itself must be >= 0 with every row sum <= 2^26 (mi355_boot_counts' rows sum to n): the kernels add them in
+ * int32 and in the halves of one int64, and the values live on the device, so the launchers cannot check them.
+ *   mi355_boot_counts_lds_max: the longest row whose histogram is kept in LDS; longer rows use global integer adds.
+ *   mi355_boot_counts: replicate r = 1 .. R makes n draws; draw k is word k & 3 of Philox4x32-10 (Salmon et al., SC 2011;
+ *     multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with counter (k >> 2, r, 0, 0) and key
+ *     (seed & 0xffffffff, seed >> 32); idx = (uint64(word) * n) >> 32 and counts[r][idx] += 1, so every row sums to n.  An
+ *     index is hit by floor(2^32 / n) or that + 1 of the 2^32 words: the map's bias is at most n / 2^32 relative (< 1.6 %
+ *     at the largest n, 1e-6 at n = 4096).  Integer adds only: the counts do not depend on the order of the adds.
+ *   mi355_boot_rank: mi355_rank_metrics on the resampled multiset; scores / target / labels / thr as there.  The segments
+ *     are sorted and their tie groups found once; per (replicate, segment) the weights are gathered in rank order and
+ *     scanned.  With A_g, B_g the WEIGHTED negatives / positives up to and including group g:
+ *       counts64 int64 [R1][S][3] = P, N, U2 = sum_g (B_g - B_{g-1}) (A_g + A_{g-1})   exact, U2 <= 2 n^2
+ *       ap double [R1][S] = sum_g (p_g / P) tp_g / (tp_g + fp_g) over the groups with p_g > 0; NaN when P = 0.  Double
+ *         partials per tile of the sort, folded in the order of mi355_rank_metrics: row 0 equals its ap to the bit.
+ *     AUROC = U2 / (2 P N) is the caller's, NaN when P N = 0.  `ws` = mi355_boot_rank_ws_ints(S, len) int32 elements.
+ *   mi355_boot_confusion: cm int64 [R1][C][C], cm[r][y][p] = the weight of the samples with labels = y and pred = p (rows
+ *     the truth, columns the prediction); 1 <= C <= 64.  The class ids live on the device: a sample with pred or labels
+ *     outside 0 .. C - 1 is skipped and its weight counted in bad int64 [R1].  With C = 2 and two models' 0 / 1
+ *     correctness as (pred, labels), row 0 is their McNemar table.
+ *   mi355_boot_sums: values double [M][n] -> sum double [R1][M] = sum_i counts[r][i] values[m][i] and weight int64 [R1][M]
+ *     = sum_i counts[r][i], both over the samples whose value is not NaN.  Folded in a fixed order.
+ *   mi355_boot_interval: reps double [R1][K] -> out double [K][6] = point (row 0), mean, se, lo, hi, valid over rows
+ *     1 .. R, R <= 8192, NaN replicates counted out (valid = those left).  mean and se (ddof = 1) by the two-pass formula in
+ *     a fixed order over the sorted replicates; lo, hi = the lo_q, hi_q quantiles by numpy's method="linear".  The
+ *     percentile interval is the only kind.  valid = 0: NaN; valid = 1: se NaN, lo = hi.
+ *   mi355_delong: scores fp32 [M][C][n] (model, class, sample), labels int32 [n]; the positives of segment (m, c) are
+ *     labels == c.  DeLong, DeLong and Clarke-Pearson's (1988) structural components from the sort, after Sun and Xu (2014):
+ *       v2 int64 [M][C][n]: a positive in tie group g: A_g + A_{g-1} (twice the negatives below it, ties half); a negative:
+ *         2 (P - B_g) + (B_g - B_{g-1}) (twice the positives above it, ties half).  Exact.
+ *       pnu int64 [M][C][3] = P, N, U2
+ *       cov double [C][M][M] = cov(V10_a, V10_b) / P + cov(V01_a, V01_b) / N with V10 = v2 / (2 N) on the positives, V01 =
+ *         v2 / (2 P) on the negatives, ddof = 1, two-pass, fixed order; var double [M][C] its diagonal.  NaN where P < 2
+ *         or N < 2.
+ *     `ws` = mi355_delong_ws_ints(M, C, n) int32 elements.
+ * Every launcher validates before it touches the device (MI355_ERR_ARG + last_error; the *_ws_ints give -1 + last_error).
+ * No floating-point atomics, no allocation, no sync, no host read-back; grids depend on the shapes alone; bit-reproducible.
+ * R >= 1, n >= 1, R1 * n <= 2^26; segments as for the sort (S * n <= 2^26). */
+int mi355_boot_counts_lds_max(void);
+int mi355_boot_counts(uint64_t seed, int R, long long n, int32_t* counts, mi355_stream_t s);
+int mi355_boot_rank_ws_ints(int S, long long len);
+int mi355_boot_rank(const float* scores, const float* target, const int32_t* labels, int S, long long len, float thr,
+                    const int32_t* counts, int R1, int32_t* ws, long long ws_ints, int64_t* counts64, double* ap,
+                    mi355_stream_t s);
+int mi355_boot_confusion(const int32_t* pred, const int32_t* labels, long long n, int C, const int32_t* counts, int R1,
+                         int64_t* cm, int64_t* bad, mi355_stream_t s);
+int mi355_boot_sums(const double* values, int M, long long n, const int32_t* counts, int R1, double* sum, int64_t* weight,
+                    mi355_stream_t s);
+int mi355_boot_interval(const double* reps, int R1, int K, double lo_q, double hi_q, double* out, mi355_stream_t s);
+int mi355_delong_ws_ints(int M, int C, long long n);
+int mi355_delong(const float* scores, const int32_t* labels, int M, int C, long long n, int32_t* ws, long long ws_ints,
+                 int64_t* v2, int64_t* pnu, double* var, double* cov, mi355_stream_t s);
 
 /* ---- optimiser on flat fp32 buffers (utils/helpers.py:251,304,332-336) ---------------------- */
 /* sumsq partials of a flat gradient buffer; nblocks = mi355_rowreduce_blocks(n). */

@@ -23,7 +23,7 @@ F32, BF16, F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
 _CTYPES = {
-    "int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong,
+    "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
     "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64, "mi355_stream_t": ctypes.c_void_p,
 }
 

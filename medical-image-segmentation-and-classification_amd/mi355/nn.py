@@ -306,6 +306,78 @@ def _rank_metrics(scores, target, labels, threshold, curve=False):
     return counts, ap, pts
 
 
+def _ws_ints(name, *shape):
+    need = lib.raw(name)(*shape)
+    if need <= 0:
+        raise RuntimeError(f"{name} failed: {lib.raw('mi355_last_error')().decode()}")
+    return need
+
+
+def _boot_counts(n, replicates, seed, device):
+    """mi355_boot_counts -> int32 [replicates + 1, n] multinomial resample weights, row 0 all ones (csrc/resample.hip)."""
+    counts = torch.empty(replicates + 1, n, dtype=torch.int32, device=device)
+    lib.mi355_boot_counts(int(seed) & 0xFFFFFFFFFFFFFFFF, replicates, n, counts)
+    return counts
+
+
+def _boot_rank(scores, target, labels, threshold, counts):
+    """mi355_boot_rank on a contiguous fp32 device tensor [S, len] with ``target`` or ``labels`` as for _rank_metrics and int32 weights
+    [R1, len] -> (int64 [R1, S, 3] = P, N, U2, float64 [R1, S] = ap).  No host round trip."""
+    S, n = scores.shape
+    R1 = counts.shape[0]
+    need = _ws_ints("mi355_boot_rank_ws_ints", S, n)
+    dev = scores.device
+    ws = torch.empty(need, dtype=torch.int32, device=dev)
+    pnu = torch.empty(R1, S, 3, dtype=torch.int64, device=dev)
+    ap = torch.empty(R1, S, dtype=torch.float64, device=dev)
+    lib.mi355_boot_rank(scores, target, labels, S, n, float(threshold), counts, R1, ws, need, pnu, ap)
+    return pnu, ap
+
+
+def _boot_confusion(pred, labels, classes, counts):
+    """mi355_boot_confusion on int32 device tensors [n] and weights [R1, n] -> (int64 [R1, C, C], rows the truth; int64 [R1] = the
+    weight of the samples skipped for a class id outside 0 .. C - 1)."""
+    R1, n = counts.shape
+    cm = torch.empty(R1, classes, classes, dtype=torch.int64, device=pred.device)
+    bad = torch.empty(R1, dtype=torch.int64, device=pred.device)
+    lib.mi355_boot_confusion(pred, labels, n, classes, counts, R1, cm, bad)
+    return cm, bad
+
+
+def _boot_sums(values, counts):
+    """mi355_boot_sums on a contiguous float64 device tensor [M, n] and weights [R1, n] -> (float64 [R1, M] weighted sums, int64
+    [R1, M] weights), both over the non-NaN values."""
+    M, n = values.shape
+    R1 = counts.shape[0]
+    total = torch.empty(R1, M, dtype=torch.float64, device=values.device)
+    weight = torch.empty(R1, M, dtype=torch.int64, device=values.device)
+    lib.mi355_boot_sums(values, M, n, counts, R1, total, weight)
+    return total, weight
+
+
+def _boot_interval(reps, lo_q, hi_q):
+    """mi355_boot_interval on a contiguous float64 device tensor [R1, K] -> float64 [K, 6] = point, mean, se, lo, hi, valid."""
+    R1, K = reps.shape
+    out = torch.empty(K, 6, dtype=torch.float64, device=reps.device)
+    lib.mi355_boot_interval(reps, R1, K, float(lo_q), float(hi_q), out)
+    return out
+
+
+def _delong(scores, labels):
+    """mi355_delong on a contiguous fp32 device tensor [M, C, n] and int32 labels [n] -> (v2 int64 [M, C, n], pnu int64 [M, C, 3],
+    var float64 [M, C], cov float64 [C, M, M]).  No host round trip."""
+    M, C, n = scores.shape
+    need = _ws_ints("mi355_delong_ws_ints", M, C, n)
+    dev = scores.device
+    ws = torch.empty(need, dtype=torch.int32, device=dev)
+    v2 = torch.empty(M, C, n, dtype=torch.int64, device=dev)
+    pnu = torch.empty(M, C, 3, dtype=torch.int64, device=dev)
+    var = torch.empty(M, C, dtype=torch.float64, device=dev)
+    cov = torch.empty(C, M, M, dtype=torch.float64, device=dev)
+    lib.mi355_delong(scores, labels, M, C, n, ws, need, v2, pnu, var, cov)
+    return v2, pnu, var, cov
+
+
 def _cls_calibration(x, labels, bins, is_prob):
     """mi355_cls_calibration on a contiguous fp32 device tensor [N, C] and int32 labels [N] -> (bin_count int64 [bins], bin_correct
     int64 [bins], bin_conf float64 [bins], out float64 [3] = NLL, Brier, ECE, scores_t fp32 [C, N]).  No host round trip."""

@@ -187,7 +187,71 @@ def _nanmean(values):
     return (float(v[ok].mean()) if ok.any() else float("nan")), int(ok.sum())
 
 
+# ---- bootstrap intervals and paired tests (nothing in the reference; utils/resample.py, DESIGN.md "Resampling statistics") ----------
+class CI:
+    """The bootstrap settings of a tester run: ``replicates`` resamples of the test set (1 .. 8192), percentile intervals at ``level``,
+    the generator's ``seed``.  Both loops accept it (or the bare number of replicates) as ``ci=``.  One object handed to several
+    models makes their resamples the same, and ``kept[model_name]`` then holds what ``print_paired_tests`` compares: per-sample
+    predictions, labels and class scores or Dice values, and the replicates of accuracy / macro AUROC / Dice — all device tensors."""
+
+    def __init__(self, replicates, level=0.95, seed=0):
+        if int(replicates) != replicates or not 1 <= replicates <= 8192:
+            raise ValueError(f"ci: the number of bootstrap replicates must be an integer in 1..8192, got {replicates}")
+        if not 0.0 < level < 1.0:
+            raise ValueError(f"ci: 0 < level < 1 expected, got {level}")
+        self.replicates, self.level, self.seed, self.kept = int(replicates), float(level), int(seed), {}
+
+    def footer(self):
+        return f"Bootstrap: {self.replicates} replicates, {self.level * 100:g}% percentile intervals, seed {self.seed}"
+
+
+def _check_ci(ci):
+    """None / 0 -> None, a CI -> itself, R or (R, level, seed) -> CI"""
+    if ci is None or isinstance(ci, CI):
+        return ci
+    if isinstance(ci, (tuple, list)):
+        return CI(*ci)
+    return None if ci == 0 else CI(ci)
+
+
+def _nanmean_rows(x):
+    """float64 device tensor [R1, C] -> [R1]: the mean over the defined entries of a row, added in column order.  _nanmean's
+    numpy mean adds in that order too while there are fewer than 8 terms (pairwise above that): row 0 equals its result to the bit for
+    the project's three classes, within (C + 1) 2^-53 relative for more than seven."""
+    ok = ~torch.isnan(x)
+    total, count = torch.zeros_like(x[:, 0]), torch.zeros_like(x[:, 0])
+    for c in range(x.shape[1]):
+        total = total + torch.where(ok[:, c], x[:, c], torch.zeros_like(total))
+        count = count + ok[:, c].double()
+    return total / count
+
+
+def _intervals(names, reps, ci, extra=None):
+    """replicates [R1, K] on the device -> {name: {"point", "mean", "se", "lo", "hi", "valid"}} of floats: one launch, one read-back.
+    ``extra`` (a float64 device tensor [E]) rides along in that read-back: -> (the dictionary, float64 numpy [E])."""
+    from utils import resample
+    iv = resample.interval(reps, ci.level)
+    keys = ("point", "mean", "se", "lo", "hi", "valid")
+    flat = torch.cat([iv[k] for k in keys] + ([extra.double().reshape(-1)] if extra is not None else [])).cpu().numpy()
+    K = len(names)
+    detail = {name: {k: float(flat[j * K + i]) for j, k in enumerate(keys)} for i, name in enumerate(names)}
+    return detail if extra is None else (detail, flat[len(keys) * K:].copy())
+
+
+def _ci_text(detail, key, fmt, scale=1.0):
+    """' [lo, hi]' in the metric's own format, or '' without intervals"""
+    if detail is None or key not in detail:
+        return ""
+    return f" [{detail[key]['lo'] * scale:{fmt}}, {detail[key]['hi'] * scale:{fmt}}]"
+
+
 def test_classification_model(model, test_loader, device, model_name, tta=None, auc=False, calibration_bins=15):
+    """The classification eval loop with the argument list its callers know: evaluate_classification_model without bootstrap intervals,
+    which documents every option."""
+    return evaluate_classification_model(model, test_loader, device, model_name, tta=tta, auc=auc, calibration_bins=calibration_bins)
+
+
+def evaluate_classification_model(model, test_loader, device, model_name, tta=None, auc=False, calibration_bins=15, ci=None):
     """``tta`` (a preset name or a list of views, utils/tta.py; or pass ``utils.tta.TTAClassifier(model, views)`` as the model): the
     predictions are the argmax of the views' mean softmax, and the result gains ``tta_agreement`` (%, the mean share of views whose
     own argmax is the prediction) and ``tta_views``.
@@ -195,8 +259,15 @@ def test_classification_model(model, test_loader, device, model_name, tta=None, 
     ranking call after it (utils/ranking.py, one segment per class, one-vs-rest) add ``auroc`` and ``average_precision`` (fractions in
     [0, 1]: the macro mean over the classes where they are defined — a class with no sample, or for auroc with every sample, is left
     out), ``auc_classes`` (how many classes entered the auroc mean), ``auroc_per_class``, ``ap_per_class`` and the calibration figures
-    ``ece`` (over ``calibration_bins`` confidence bins), ``brier`` and ``nll``."""
+    ``ece`` (over ``calibration_bins`` confidence bins), ``brier`` and ``nll``.
+    ``ci`` (a ``CI``, or the number of bootstrap replicates): the predictions, labels and scores that are on the device anyway are
+    resampled there (utils/resample.py: one weights call, one confusion call, with ``auc`` one ranking and one DeLong call, one
+    interval call, one read-back).  The result gains ``<key>_ci`` = (lo, hi) and ``<key>_se`` for accuracy, precision, recall, f1
+    and, with ``auc``, auroc and average_precision; ``auroc_ci_per_class`` / ``auroc_se_per_class``; ``auroc_delong_ci_per_class``
+    (auc -+ z sqrt(DeLong's variance), clipped to [0, 1]); ``ci_detail`` ({name: point, mean, se, lo, hi, valid}: ``point`` is the
+    same code on the identity resample) and ``ci_replicates`` / ``ci_level`` / ``ci_seed``; every printed figure its `` [lo, hi]``."""
     from utils.tta import TTAClassifier
+    ci = _check_ci(ci)
     model.eval()
     preds, labels, agree, kept_scores = [], [], [], []
     print(f"\n{'=' * 60}\nTesting Classification Model: {model_name}\n{'=' * 60}")
@@ -218,7 +289,9 @@ def test_classification_model(model, test_loader, device, model_name, tta=None, 
                 if auc:
                     kept_scores.append(r["probs"].float())
             labels.append(y.to(device))
-    m = calculate_classification_metrics(torch.cat(preds).cpu().numpy(), torch.cat(labels).cpu().numpy())
+    preds_dev, labels_dev = torch.cat(preds), torch.cat(labels)
+    preds_host, labels_host = preds_dev.cpu().numpy(), labels_dev.cpu().numpy()
+    m = calculate_classification_metrics(preds_host, labels_host)
     if tta is not None:
         m["tta_views"] = len(cls_tta.views)
         m["tta_agreement"] = float(torch.cat(agree).double().mean().cpu()) / m["tta_views"] * 100
@@ -232,23 +305,63 @@ def test_classification_model(model, test_loader, device, model_name, tta=None, 
         m["auroc"], m["auc_classes"] = _nanmean(m["auroc_per_class"])
         m["average_precision"] = _nanmean(m["ap_per_class"])[0]
         m["ece"], m["brier"], m["nll"] = float(cal["ece"].cpu()), float(cal["brier"].cpu()), float(cal["nll"].cpu())
+    d = None
+    if ci is not None:
+        from statistics import NormalDist
+        from utils import resample
+        p_dev, y_dev = preds_dev.to(torch.int32), labels_dev.to(torch.int32)
+        # without scores the class ids are taken as they are: the largest one seen, from the arrays the metrics above read back
+        classes = cal["scores_t"].shape[0] if auc else int(max(preds_host.max(), labels_host.max())) + 1
+        counts = resample.bootstrap_counts(p_dev.shape[0], ci.replicates, ci.seed, device=p_dev.device)
+        cls = resample.classification_from_confusion(resample.boot_confusion(p_dev, y_dev, classes, counts)[0])
+        names = ["accuracy", "precision", "recall", "f1"]
+        cols = [cls[k] for k in names]
+        kept = {"pred": p_dev, "labels": y_dev, "accuracy": cls["accuracy"], "scores_t": None, "auroc": None}
+        if auc:
+            rk_b = resample.boot_rank_metrics(cal["scores_t"], counts, labels=y_dev)
+            macro = _nanmean_rows(rk_b["auroc"])
+            names += ["auroc", "average_precision"] + [f"auroc_class{c}" for c in range(classes)]
+            cols += [macro, _nanmean_rows(rk_b["average_precision"])] + list(rk_b["auroc"].unbind(1))
+            var = resample.delong(cal["scores_t"], y_dev)["var"][0]
+            kept.update(scores_t=cal["scores_t"], auroc=macro)
+            d, var = _intervals(names, torch.stack(cols, 1), ci, extra=var)       # DeLong's variances ride along in the one read-back
+        else:
+            d = _intervals(names, torch.stack(cols, 1), ci)
+        for k in names[:6]:
+            m[f"{k}_ci"], m[f"{k}_se"] = (d[k]["lo"], d[k]["hi"]), d[k]["se"]
+        if auc:
+            per = [d[f"auroc_class{c}"] for c in range(classes)]
+            m["auroc_ci_per_class"] = np.array([[e["lo"], e["hi"]] for e in per])
+            m["auroc_se_per_class"] = np.array([e["se"] for e in per])
+            half = NormalDist().inv_cdf(0.5 + ci.level / 2.0) * np.sqrt(var)
+            m["auroc_delong_ci_per_class"] = np.stack([np.clip(m["auroc_per_class"] - half, 0.0, 1.0),
+                                                       np.clip(m["auroc_per_class"] + half, 0.0, 1.0)], 1)
+        m["ci_detail"], m["ci_replicates"], m["ci_level"], m["ci_seed"] = d, ci.replicates, ci.level, ci.seed
+        ci.kept[model_name] = kept
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
-    print(f"Accuracy:  {m['accuracy']:.2f}%\nPrecision: {m['precision']:.2f}%\nRecall:    {m['recall']:.2f}%\nF1 Score:  {m['f1']:.2f}%")
+    print(f"Accuracy:  {m['accuracy']:.2f}%{_ci_text(d, 'accuracy', '.2f')}\nPrecision: {m['precision']:.2f}%{_ci_text(d, 'precision', '.2f')}\n"
+          f"Recall:    {m['recall']:.2f}%{_ci_text(d, 'recall', '.2f')}\nF1 Score:  {m['f1']:.2f}%{_ci_text(d, 'f1', '.2f')}")
     if tta is not None:
         print(f"TTA agreement: {m['tta_agreement']:.2f}% of {m['tta_views']} views")
     if auc:
-        print(f"AUROC / AP: {m['auroc']:.4f} / {m['average_precision']:.4f} (macro, one-vs-rest, {m['auc_classes']} classes)")
+        print(f"AUROC / AP: {m['auroc']:.4f}{_ci_text(d, 'auroc', '.4f')} / {m['average_precision']:.4f}{_ci_text(d, 'average_precision', '.4f')}"
+              f" (macro, one-vs-rest, {m['auc_classes']} classes)")
         print(f"ECE ({calibration_bins} bins) / Brier / NLL: {m['ece']:.4f} / {m['brier']:.4f} / {m['nll']:.4f}")
     print("\nPer-Class Metrics:")
     for i, c in enumerate(CLASSES[:len(m["f1_per_class"])]):   # (the reference indexes all of CLASSES, tester.py:282-296, and dies when a class is absent)
+        delong_text = ""
+        if d is not None and auc and i < len(m["auroc_per_class"]):
+            delong_text = f"{_ci_text(d, f'auroc_class{i}', '.4f')} (DeLong [{m['auroc_delong_ci_per_class'][i, 0]:.4f}, {m['auroc_delong_ci_per_class'][i, 1]:.4f}])"
         print(f"\n{c}:\n  Precision: {m['precision_per_class'][i]:.2f}%\n  Recall:    {m['recall_per_class'][i]:.2f}%\n"
               f"  F1 Score:  {m['f1_per_class'][i]:.2f}%"
-              + (f"\n  AUROC:     {m['auroc_per_class'][i]:.4f}\n  AP:        {m['ap_per_class'][i]:.4f}"
+              + (f"\n  AUROC:     {m['auroc_per_class'][i]:.4f}{delong_text}\n  AP:        {m['ap_per_class'][i]:.4f}"
                  if auc and i < len(m["auroc_per_class"]) else ""))
     print("\nConfusion Matrix:")
     print((" " * 25).join(f"{c:>12}" for c in CLASSES))      # the reference's header: names joined by 12 + 1 + 12 blanks (:299)
     for i, row in enumerate(m["confusion_matrix"][:len(CLASSES)]):
         print(f"{CLASSES[i]:<12}" + "".join(f"{v:>12}" for v in row))
+    if ci is not None:
+        print(ci.footer())
     print(f"{'=' * 60}\n")
     return m
 
@@ -260,6 +373,12 @@ def test_segmentation_model(model, test_loader, device, model_name, surface=Fals
 
 
 def evaluate_segmentation_model(model, test_loader, device, model_name, surface=False, auc=False):
+    """The segmentation eval loop with ``auc``, under the argument list its callers know: evaluate_segmentation_model_ci without bootstrap
+    intervals, which documents every option."""
+    return evaluate_segmentation_model_ci(model, test_loader, device, model_name, surface=surface, auc=auc)
+
+
+def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surface=False, auc=False, ci=None):
     """``surface=True`` adds hausdorff, hd95, assd (pixels; mean over the samples where both masks have a border), surface_dice
     (%, tolerance 2 pixels) and surface_samples (how many samples entered those means) behind the six overlap metrics.
     Test-time augmentation: pass ``utils.tta.TTASegmenter(model, views, merge)`` as the model.  Every metric is then taken from the
@@ -275,9 +394,16 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
     loader's images are then larger than the tile).  Every metric is taken from the windows' blended map, and the result gains
     ``sw_tiles`` (windows per image) and ``sw_seam_spread`` (per sample the mean, over the pixels more than one window covers, of the
     largest minus the smallest value the windows give the pixel — logits, or probabilities for ``merge="prob"``; 0 for a sample
-    without such pixels; averaged over the samples)."""
+    without such pixels; averaged over the samples).
+    ``ci`` (a ``CI``, or the number of bootstrap replicates): the per-sample values formed after the read-back — the six overlap
+    metrics, with ``surface`` the four surface metrics, with ``auc`` the pixel ROC-AUC and average precision — go back to the device
+    once as [M, n] doubles and their NaN-aware means are bootstrapped over the images (utils/resample.py).  The result gains
+    ``<key>_ci`` = (lo, hi) and ``<key>_se`` for each of them, ``ci_detail`` ({key: point, mean, se, lo, hi, valid}; ``point`` is the
+    same fold on the identity resample, equal to the plain figure up to the order of the additions) and ``ci_replicates`` /
+    ``ci_level`` / ``ci_seed``; every printed figure its `` [lo, hi]``."""
     from utils.sliding import SlidingWindowSegmenter
     from utils.tta import TTASegmenter
+    ci = _check_ci(ci)
     model.eval()
     tta = seg_tta = model if isinstance(model, TTASegmenter) else None
     sw = model if isinstance(model, SlidingWindowSegmenter) else None
@@ -319,7 +445,7 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
             if auc:
                 rk = rank_metrics(out.float().reshape(B, per), target=masks.float().reshape(B, per), threshold=0.5)
                 ranked.append((rk["auroc"], rk["average_precision"]))
-    surf = []
+    surf, rows = [], []
     if tta is not None:                           # read back with the counters below
         unanimous = torch.cat(unanimous).cpu().numpy()
     if sw is not None:
@@ -329,6 +455,8 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
             m = _metrics_from_counts(c, per)
             for k in tot:
                 tot[k] += m[k]
+            if ci is not None:
+                rows.append([m[k] for k in tot])
             n += 1
         if raw is not None:
             surf.append(_surface_from_raw(raw[0].cpu().numpy(), raw[1].cpu().numpy(), 1.0, 95))
@@ -342,6 +470,24 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
     if auc:                                       # read back with the counters above
         avg["pixel_auroc"], avg["auc_samples"] = _nanmean(torch.cat([a for a, _ in ranked]).cpu().numpy())
         avg["pixel_ap"] = _nanmean(torch.cat([p for _, p in ranked]).cpu().numpy())[0]
+    d = None
+    if ci is not None:
+        from utils import resample
+        names, values = list(tot), [np.asarray(rows, dtype=np.float64).T]
+        if surface:                               # NaN where a sample has no surface distances: counted out of every replicate's mean
+            names += list(SURFACE_KEYS)
+            values.append(np.stack([per_sample[k] * (100.0 if k == "surface_dice" else 1.0) for k in SURFACE_KEYS]))
+        per_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate(values))).to(device)
+        if auc:
+            names += ["pixel_auroc", "pixel_ap"]
+            per_dev = torch.cat([per_dev, torch.cat([a for a, _ in ranked]).view(1, -1), torch.cat([p for _, p in ranked]).view(1, -1)])
+        counts = resample.bootstrap_counts(n, ci.replicates, ci.seed, device=per_dev.device)
+        reps = resample.boot_means(per_dev, counts)
+        d = _intervals(names, reps, ci)
+        for k in names:
+            avg[f"{k}_ci"], avg[f"{k}_se"] = (d[k]["lo"], d[k]["hi"]), d[k]["se"]
+        avg["ci_detail"], avg["ci_replicates"], avg["ci_level"], avg["ci_seed"] = d, ci.replicates, ci.level, ci.seed
+        ci.kept[model_name] = {"dice_values": per_dev[names.index("dice")], "dice": reps[:, names.index("dice")]}
     if tta is not None:
         avg["tta_unanimous"] = float(unanimous.mean()) * 100
         avg["tta_views"] = len(seg_tta.views)
@@ -349,14 +495,20 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
         avg["sw_tiles"] = int(sw_tiles)
         avg["sw_seam_spread"] = float(seam.mean())
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
-    print(f"IoU (Jaccard):     {avg['iou']:.2f}%\nDice Coefficient:  {avg['dice']:.2f}%\nPixel Accuracy:    {avg['pixel_accuracy']:.2f}%")
-    print(f"Precision:         {avg['precision']:.2f}%\nRecall:            {avg['recall']:.2f}%\nF1 Score:          {avg['f1']:.2f}%"
-          + (f"\nHausdorff:         {avg['hausdorff']:.2f} px\nHD95:              {avg['hd95']:.2f} px\nASSD:              {avg['assd']:.2f} px\n"
-             f"Surface Dice @2px: {avg['surface_dice']:.2f}% ({avg['surface_samples']} of {n} samples)" if surface else "")
-          + (f"\nPixel AUROC / AP:  {avg['pixel_auroc']:.4f} / {avg['pixel_ap']:.4f} ({avg['auc_samples']} of {n} samples)" if auc else "")
+    b = lambda key, fmt=".2f": _ci_text(d, key, fmt)      # noqa: E731  ('' without ci)
+    print(f"IoU (Jaccard):     {avg['iou']:.2f}%{b('iou')}\nDice Coefficient:  {avg['dice']:.2f}%{b('dice')}\n"
+          f"Pixel Accuracy:    {avg['pixel_accuracy']:.2f}%{b('pixel_accuracy')}")
+    print(f"Precision:         {avg['precision']:.2f}%{b('precision')}\nRecall:            {avg['recall']:.2f}%{b('recall')}\n"
+          f"F1 Score:          {avg['f1']:.2f}%{b('f1')}"
+          + (f"\nHausdorff:         {avg['hausdorff']:.2f} px{b('hausdorff')}\nHD95:              {avg['hd95']:.2f} px{b('hd95')}\n"
+             f"ASSD:              {avg['assd']:.2f} px{b('assd')}\n"
+             f"Surface Dice @2px: {avg['surface_dice']:.2f}%{b('surface_dice')} ({avg['surface_samples']} of {n} samples)" if surface else "")
+          + (f"\nPixel AUROC / AP:  {avg['pixel_auroc']:.4f}{b('pixel_auroc', '.4f')} / {avg['pixel_ap']:.4f}{b('pixel_ap', '.4f')} "
+             f"({avg['auc_samples']} of {n} samples)" if auc else "")
           + (f"\nTTA unanimous:     {avg['tta_unanimous']:.2f}% of the pixels ({avg['tta_views']} views, merged {tta_merge})" if tta is not None else "")
           + (f"\nSliding window:    {avg['sw_tiles']} tiles of {sw.tile} px per image (overlap {sw.overlap:g}, {sw.weighting} weights, merged "
              f"{sw.merge}), seam spread {avg['sw_seam_spread']:.4f}" if sw is not None else "")
+          + (f"\n{ci.footer()}" if ci is not None else "")
           + f"\n{'=' * 60}\n")
     return avg
 
@@ -369,8 +521,8 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, auc=False, calibration_bins=15,
-                    surface=False):
+                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, ci=None, auc=False,
+                    calibration_bins=15, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -386,8 +538,12 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     segmenter (evaluate_segmentation_model(auc=True)).  ``sliding=(tile, overlap, weighting)``: the segmenters are handed on wrapped in
     utils.sliding.SlidingWindowSegmenter (windows of ``tile`` pixels blended on the GPU; the classifiers are untouched), and ``size``
     (default IMG_SIZE, at least ``tile``) is the side the default SEGMENTATION loader resizes to (the classifiers keep IMG_SIZE) — the
-    point of the option is a ``size`` above the training size with ``tile`` at the training size.  ``sliding`` together with ``tta``: ValueError."""
+    point of the option is a ``size`` above the training size with ``tile`` at the training size.  ``sliding`` together with ``tta``: ValueError.
+    ``ci`` (a ``CI``, the number of bootstrap replicates, or (replicates, level, seed)): every figure of every model gets its
+    bootstrap interval (the ``ci`` of the two loops).  All models share the seed, hence the resamples, and what ``print_paired_tests``
+    needs stays on the device in ``ci.kept`` — pass a ``CI`` to have it afterwards."""
     from utils.helpers import get_class_model, get_seg_model
+    ci = _check_ci(ci)
     size = IMG_SIZE if size is None else int(size)
     if size < 1:
         raise ValueError(f"size >= 1 required, got {size}")
@@ -459,6 +615,8 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         cls_test = (lambda m, l, d, name: test_classification_model(m, l, d, name, tta=tta)) if tta is not None else test_classification_model
         if auc:
             cls_test = lambda m, l, d, name: test_classification_model(m, l, d, name, tta=tta, auc=True, calibration_bins=calibration_bins)  # noqa: E731
+        if ci is not None:
+            cls_test = lambda m, l, d, name: evaluate_classification_model(m, l, d, name, tta=tta, auc=auc, calibration_bins=calibration_bins, ci=ci)  # noqa: E731
         run(_CLS_FILES, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], cls_test, "Classification")
     if seg_loader is None:
         print(f"\n[WARNING] Segmentation test dataset not found: no loader given for {DATA_ROOT!r}")
@@ -478,6 +636,14 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             sw_batch = max(1, batch_size // 2)
             sw_wrap = lambda m: SlidingWindowSegmenter(m, sliding[0], sliding[1], sliding[2], batch=sw_batch)  # noqa: E731
             seg_test = lambda m, l, d, name: evaluate_segmentation_model(sw_wrap(m), l, d, name, surface=surface, auc=auc)  # noqa: E731
+        if ci is not None:
+            if sliding is not None:
+                seg_wrap = sw_wrap
+            elif tta is not None:
+                seg_wrap = lambda m: TTASegmenter(m, tta, tta_merge)  # noqa: E731
+            else:
+                seg_wrap = lambda m: m  # noqa: E731
+            seg_test = lambda m, l, d, name: evaluate_segmentation_model_ci(seg_wrap(m), l, d, name, surface=surface, auc=auc, ci=ci)  # noqa: E731
         run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
     return results
 
@@ -543,6 +709,72 @@ def print_summary(results):
     print("=" * 80 + "\n")
 
 
+def print_paired_tests(results, ci):
+    """After ``test_all_models(ci=CI(...))`` (or the two loops with one ``CI``): every model against the best of its task ON THE SAME
+    RESAMPLES, so the differences are paired.  Classifiers: the accuracy difference (percentage points) with its bootstrap interval
+    and McNemar's exact p; with ``auc`` the macro-AUROC difference with its interval and DeLong's p per class ("identical" where the
+    two rankings give a zero variance of the difference).  Segmenters: the Dice difference with its interval.  Returns the rows:
+    {(model, best): {"d_accuracy", "d_accuracy_ci", "mcnemar", "d_auroc", "d_auroc_ci", "delong", "d_dice", "d_dice_ci"}}."""
+    from utils import resample
+    ci = _check_ci(ci)
+    rows = {}
+    if ci is None or not ci.kept:
+        return rows
+    fmt = lambda dd, f: f"{dd['point']:+{f}} [{dd['lo']:+{f}}, {dd['hi']:+{f}}]"      # noqa: E731
+    cls_models = [m for m in results if m in ci.kept and "pred" in ci.kept[m]]
+    seg_models = [m for m in results if m in ci.kept and "dice" in ci.kept[m]]
+    print("\n" + "=" * 80 + "\n" + " " * 22 + "PAIRED COMPARISONS (same resamples)\n" + "=" * 80)
+    if len(cls_models) > 1:
+        best = max(cls_models, key=lambda x: results[x]["accuracy"])
+        kb = ci.kept[best]
+        print(f"\nCLASSIFICATION MODELS against {best}:\n" + "-" * 80)
+        for name in cls_models:
+            if name == best:
+                continue
+            k = ci.kept[name]
+            diffs, names = [k["accuracy"] - kb["accuracy"]], ["d_accuracy"]
+            both_auc = k["auroc"] is not None and kb["auroc"] is not None
+            if both_auc:
+                diffs.append(k["auroc"] - kb["auroc"])
+                names.append("d_auroc")
+            d = _intervals(names, torch.stack(diffs, 1), ci)
+            mc = resample.mcnemar(k["pred"] == k["labels"], kb["pred"] == kb["labels"])
+            row = {"d_accuracy": d["d_accuracy"]["point"], "d_accuracy_ci": (d["d_accuracy"]["lo"], d["d_accuracy"]["hi"]), "mcnemar": mc}
+            print(f"{name:<16} accuracy {fmt(d['d_accuracy'], '.2f')} points, McNemar p = {mc['p']:.4g} ({mc['b']} / {mc['c']} discordant)")
+            if both_auc:
+                row.update(d_auroc=d["d_auroc"]["point"], d_auroc_ci=(d["d_auroc"]["lo"], d["d_auroc"]["hi"]),
+                           delong=resample.delong_test(k["scores_t"], kb["scores_t"], k["labels"]))
+                per = ", ".join(f"{CLASSES[c] if c < len(CLASSES) else c}: " + ("identical" if t["z"] != t["z"] else f"p = {t['p']:.4g}")
+                                for c, t in enumerate(row["delong"]))
+                print(f"{'':<16} macro AUROC {fmt(d['d_auroc'], '.4f')}; DeLong {per}")
+            rows[(name, best)] = row
+    if len(seg_models) > 1:
+        best = max(seg_models, key=lambda x: results[x]["dice"])
+        print(f"\nSEGMENTATION MODELS against {best}:\n" + "-" * 80)
+        for name in seg_models:
+            if name == best:
+                continue
+            d = _intervals(["d_dice"], (ci.kept[name]["dice"] - ci.kept[best]["dice"]).view(-1, 1), ci)["d_dice"]
+            rows[(name, best)] = {"d_dice": d["point"], "d_dice_ci": (d["lo"], d["hi"])}
+            print(f"{name:<16} Dice {fmt(d, '.2f')} points")
+    print(ci.footer() + "\n" + "=" * 80 + "\n")
+    return rows
+
+
+def _csv_row(name, result):
+    """scalars only; a ``<key>_ci`` pair becomes the columns ``<key>_lo`` and ``<key>_hi``"""
+    row = {"Model": name}
+    for k, v in result.items():
+        if k.endswith("_ci") and isinstance(v, tuple):
+            row[k[:-3] + "_lo"], row[k[:-3] + "_hi"] = v
+        else:
+            row[k] = v
+    for k in ("confusion_matrix", "precision_per_class", "recall_per_class", "f1_per_class", "auroc_per_class", "ap_per_class",
+              "ci_detail", "auroc_ci_per_class", "auroc_se_per_class", "auroc_delong_ci_per_class"):
+        row.pop(k, None)
+    return row
+
+
 def save_results_to_csv(results, cls_output_path="results/classification_test_results.csv",
                         seg_output_path="results/segmentation_test_results.csv"):
     """One CSV per family, a `Model` column followed by the scalar metrics in dictionary order (tester.py:808-876;
@@ -554,23 +786,13 @@ def save_results_to_csv(results, cls_output_path="results/classification_test_re
     cls_models = [k for k in results.keys() if any(x in k for x in ["ResNet18", "ResNet50", "VGG", "CLIP"]) and "Seg" not in k]
     seg_models = [k for k in results.keys() if "Unet" in k or "UNet" in k or "CLIPSeg" in k]
     if cls_models:
-        rows = []
-        for name in cls_models:
-            row = {"Model": name}
-            row.update(results[name])
-            for k in ("confusion_matrix", "precision_per_class", "recall_per_class", "f1_per_class", "auroc_per_class", "ap_per_class"):
-                row.pop(k, None)
-            rows.append(row)
+        rows = [_csv_row(name, results[name]) for name in cls_models]
         pd.DataFrame(rows).to_csv(cls_output_path, index=False)
         print(f"\n[INFO] Classification results saved to: {cls_output_path}")
     else:
         print("\n[INFO] No classification results to save.")
     if seg_models:
-        rows = []
-        for name in seg_models:
-            row = {"Model": name}
-            row.update(results[name])
-            rows.append(row)
+        rows = [_csv_row(name, results[name]) for name in seg_models]
         pd.DataFrame(rows).to_csv(seg_output_path, index=False)
         print(f"[INFO] Segmentation results saved to: {seg_output_path}")
     else:
@@ -595,6 +817,10 @@ def build_parser():
     _ap.add_argument("--auc", action="store_true",
                      help="also report ROC-AUC and average precision (per class / per image over the pixels) and the classifiers' ECE, Brier score and NLL")
     _ap.add_argument("--calibration-bins", type=int, default=15, help="--auc: confidence bins of the expected calibration error")
+    _ap.add_argument("--ci", type=int, default=0,
+                     help="bootstrap replicates (up to 8192) for a percentile interval on every figure and paired tests between the models; 0 = off")
+    _ap.add_argument("--ci-level", type=float, default=0.95, help="--ci: the level of the intervals")
+    _ap.add_argument("--ci-seed", type=int, default=0, help="--ci: the seed of the resamples (shared by every model)")
     return _ap
 
 
@@ -619,7 +845,11 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
         _kw.update(sliding=(_args.sw_tile, _args.sw_overlap, _args.sw_weight))
     if _args.size != IMG_SIZE:
         _kw["size"] = _args.size
+    if _args.ci != 0:
+        _kw["ci"] = CI(_args.ci, _args.ci_level, _args.ci_seed)
     results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
+    if _args.ci != 0:
+        print_paired_tests(results, _kw["ci"])
     save_results_to_csv(results, cls_output_path="classification_test_results.csv", seg_output_path="segmentation_test_results.csv")
     print("\n[INFO] Testing complete!")
