@@ -39,31 +39,33 @@ const char* mi355_last_error(void);
 
 /* ---- layout staging ------------------------------------------------------------------ */
 
-/* NCHW fp32 network input -> NHWC `dtype` with channels zero-padded to Cpad (multiple of
- * 32).  Replaces the implicit layout/precision change of `x.to(device)` + autocast,
- * utils/helpers.py:318-322. */
+/* NCHW fp32 network input -> NHWC `dtype` (one rounding to nearest even) with channels padded with +0 to Cpad (any
+ * multiple of 8 >= C; the plans use multiples of 32).  Replaces the implicit layout/precision change of
+ * `x.to(device)` + autocast, utils/helpers.py:318-322. */
 int mi355_pack_input_nchw(const float* x, void* y, int N, int C, int H, int W, int Cpad, int dtype,
                           mi355_stream_t s);
 /* The same input as the 3 x 3 patches of a stride-1, pad-1 convolution: y[n][h][w][c * 9 + kh * 3 + kw] = x[n][c][h + kh - 1][w + kw - 1]
- * (zero outside the image), 32 channels per pixel, C <= 3.  The stem Conv2d(3, Co, 3, 1, 1) (AttentionUNet.py:6,60) is then a
+ * (+0 outside the image and for channels >= 9 C), 32 channels per pixel, C <= 3, any N * H below 2^31.  The stem Conv2d(3, Co, 3, 1, 1) (AttentionUNet.py:6,60) is then a
  * pointwise convolution over K = 27 -> 32 on the SAME parameter memory ([Co][3][3][3] read as [Co][27][1][1]). */
 int mi355_pack_input_im2col3(const float* x, void* y, int N, int C, int H, int W, int dtype, mi355_stream_t s);
 /* NHWC `dtype` (channel stride ld) -> NCHW fp32 (model outputs / logits). */
 int mi355_unpack_output_nchw(const void* x, float* y, int N, int C, int H, int W, int ld, int dtype,
                              mi355_stream_t s);
-/* NCHW fp32 -> NHWC `dtype` without padding (incoming output gradients). */
+/* NCHW fp32 -> NHWC `dtype` (channel stride ld >= C, C a multiple of the 16-byte chunk) without padding (incoming output
+ * gradients). */
 int mi355_pack_nchw(const float* x, void* y, int N, int C, int H, int W, int ld, int dtype, mi355_stream_t s);
 
 /* fp32 parameter [Co][Ci][KH][KW] -> packed forward weights Wf[Co][KH*KW][Cip] and (if wb != NULL)
- * packed data-gradient weights Wb[Cip][KH*KW][Co] (Cip = Ci padded up to a multiple of 32, zero
- * filled).  `transposed` != 0 reads a ConvTranspose2d parameter [Ci][Co][KH][KW] instead
+ * packed data-gradient weights Wb[Cip][KH*KW][Co] (any Cip >= Ci, the rows / columns ci >= Ci filled with +0; the plans
+ * pad Ci up to a multiple of 32).  `transposed` != 0 reads a ConvTranspose2d parameter [Ci][Co][KH][KW] instead
  * (models/segmentation_models/ResnetUnet.py:21). */
 int mi355_pack_conv_weight(const float* w, void* wf, void* wb, int Co, int Ci, int Cip, int KH, int KW,
                            int transposed, int dtype, mi355_stream_t s);
 
 /* Every weight pack of a launch plan in ONE launch: `table` = n descriptors of 9 int64 in device memory
  * {w, wf, wb (0 = none), Co, Ci, Cip, KH*KW, transposed, scale (0 = none)}, same semantics as mi355_pack_conv_weight;
- * scale[Co] multiplies the rows of the packs (eval-mode BatchNorm folded into the weights, !transposed only). */
+ * scale[Co] multiplies output channel co of both packs as one fp32 product before the rounding to `dtype` (eval-mode
+ * BatchNorm folded into the weights); a transposed descriptor ignores its scale. */
 int mi355_pack_conv_weights_batched(const int64_t* table, int n, int fields /* = 9: checked, the table is device memory */,
                                     int dtype, mi355_stream_t s);
 
@@ -261,13 +263,14 @@ int mi355_maxpool_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, in
 int mi355_maxpool_bwd(const void* x, int ldx, const void* dy, int lddy, void* dx, int lddx,
                       int N, int H, int W, int C, int k, int stride, int pad, int accumulate, int dtype,
                       mi355_stream_t s);
-/* gradient of nn.Upsample(scale_factor=2) (nearest): dx[h][w] = sum of the 2x2 block of dy. */
+/* gradient of nn.Upsample(scale_factor=2) (nearest): dx[h][w] = sum of the 2x2 block of dy (+ dx when accumulate != 0),
+ * summed in fp32 and rounded to `dtype` once; accumulate == 0 never reads dx. */
 int mi355_upsample2_bwd(const void* dy, int lddy, void* dx, int lddx, int N, int H, int W, int C,
                         int accumulate, int dtype, mi355_stream_t s);
-/* y = a + b (b optional => copy), strided. */
+/* y = a + b (b == NULL: a strided copy of a's bits), one ld per operand; y may be a or b (in place). */
 int mi355_add(const void* a, int lda, const void* b, int ldb, void* y, int ldy, long long M, int C, int dtype,
               mi355_stream_t s);
-/* y = relu(x) forward; dx = dy * (y > 0) backward (VGG.py:10). */
+/* y = relu(x) forward; dx = y > 0 ? dy : +0 backward, a select: the bits of dy pass, an inf under y <= 0 gives 0 (VGG.py:10). */
 int mi355_relu_fwd(const void* x, int ldx, void* y, int ldy, long long M, int C, int dtype, mi355_stream_t s);
 int mi355_relu_bwd(const void* dy, int lddy, const void* y, int ldy, void* dx, int lddx, long long M, int C,
                    int dtype, mi355_stream_t s);

@@ -1,5 +1,6 @@
-"""What the exact-data GPU files (tests/test_gpu_stream_exact.py, tests/test_gpu_gate_exact.py) share: guarded device buffers, the
-launch-and-compare step, the coverage ledger and the runner of child pytest processes.
+"""What the exact-data GPU files (tests/test_gpu_stream_exact.py, tests/test_gpu_gate_exact.py, tests/test_gpu_head_exact.py,
+tests/test_gpu_layout_exact.py) share: guarded device buffers, the launch-and-compare step, the coverage ledger and the runner of
+child pytest processes.
 
 Every tensor is a channel slice of a wider buffer with guard channels on both sides and guard rows behind row M - 1 (NaN in
 inputs, a sentinel in outputs); outputs are pre-filled with NaN.  After each launch: guards unchanged, no NaN, bit-equal to the
@@ -111,6 +112,100 @@ def _run(what, fn, bufs, want, twice=True):
         assert not torch.isnan(got).any(), f"{what}: {int(torch.isnan(got).sum())} elements never written (or NaN read)"
         ref = ref.reshape(got.shape)
         assert torch.equal(got, ref), f"{what}: {int((got != ref).sum())} of {got.numel()} elements differ, max |diff| {float((got - ref).abs().max())}"
+        first[b] = _bits(b.t).clone()
+    if twice:
+        for b in bufs:
+            b.reset()
+        fn()
+        torch.cuda.synchronize()
+        for b in want:
+            assert torch.equal(_bits(b.t), first[b]), f"{what}: a second launch gives other bytes"
+
+
+# ---- operands given in the storage type itself, compared by their BITS (-0.0, inf and subnormals count) ---------------------------
+class Slice:
+    """[M + guard rows][g + C + g] of `dtype` on the device, the body a channel slice (ld = C + 2 g).  `body` is a tensor of `dtype`
+    itself (its bits are kept).  body given: an input (guards NaN; the launch must leave every byte alone) or, with inout, an
+    output that is also read (guards = sentinel); body None: an output (body NaN, guards = sentinel)."""
+
+    def __init__(self, M, C, dtype, gr, body=None, inout=False, g=G):
+        assert g % 8 == 0                                  # the slice stays 16-byte aligned
+        self.M, self.C, self.g, self.input = M, C, g, body is not None and not inout
+        w = torch.full((M + gr, C + 2 * g), NAN if self.input else SENT, dtype=dtype)
+        if body is None:
+            w[:M, g:g + C] = NAN
+        else:
+            assert body.dtype == dtype and tuple(body.shape) == (M, C), (body.dtype, tuple(body.shape), M, C)
+            w[:M, g:g + C] = body
+        self.init = w.to(DEV)
+        self.t = self.init.clone()
+        self.ptr = self.t.data_ptr() + g * self.t.element_size()
+        self.ld = C + 2 * g
+
+    def reset(self):
+        self.t.copy_(self.init)
+
+    def raw(self):
+        return self.t[:self.M, self.g:self.g + self.C].cpu().contiguous()
+
+    def untouched(self):
+        return torch.equal(_bits(self.t), _bits(self.init))
+
+    def guards_ok(self):
+        if self.input:
+            return self.untouched()
+        a = self.t.clone()
+        a[:self.M, self.g:self.g + self.C] = self.init[:self.M, self.g:self.g + self.C]
+        return torch.equal(_bits(a), _bits(self.init))
+
+
+class Pad(Slice):
+    """a contiguous buffer of n elements of any float `dtype` between two pads of PADW elements (fp32 NCHW tensors, weight packs,
+    the fixed-ld outputs of the input packs): input, output or inout as in Slice"""
+    PADW = 64
+
+    def __init__(self, n, dtype, body=None, inout=False):
+        p = self.PADW
+        self.M, self.C, self.g, self.n, self.input = 1, n, p, n, body is not None and not inout
+        w = torch.full((n + 2 * p,), NAN if self.input else SENT, dtype=dtype)
+        if body is None:
+            w[p:p + n] = NAN
+        else:
+            assert body.dtype == dtype and body.numel() == n, (body.dtype, body.numel(), n)
+            w[p:p + n] = body.reshape(-1)
+        self.init = w.to(DEV)
+        self.t = self.init.clone()
+        self.ptr = self.t.data_ptr() + p * self.t.element_size()
+
+    def raw(self):
+        return self.t[self.g:self.g + self.n].cpu()
+
+    def guards_ok(self):
+        if self.input:
+            return self.untouched()
+        a = self.t.clone()
+        a[self.g:self.g + self.n] = self.init[self.g:self.g + self.n]
+        return torch.equal(_bits(a), _bits(self.init))
+
+
+def _run_bits(what, fn, bufs, want, twice=True):
+    """launch; guards of every Slice / Pad in `bufs`; no NaN; the BITS of each output equal those of want {buffer: reference in the
+    storage type}; a second launch from the same start gives the same bytes"""
+    fn()
+    torch.cuda.synchronize()
+    for i, b in enumerate(bufs):
+        assert b.guards_ok(), f"{what}: guards of buffer {i} changed"
+    first = {}
+    for b, ref in want.items():
+        got = b.raw()
+        assert not torch.isnan(got).any(), f"{what}: {int(torch.isnan(got).sum())} elements never written (or NaN read)"
+        assert ref.dtype == got.dtype, (ref.dtype, got.dtype)
+        ref = ref.reshape(got.shape)
+        bad = _bits(got) != _bits(ref.contiguous())
+        if bool(bad.any()):
+            k = torch.nonzero(bad)[0].tolist()
+            raise AssertionError(f"{what}: {int(bad.sum())} of {got.numel()} elements differ in their bits, first at {k}: "
+                                 f"got {float(got[tuple(k)])!r}, want {float(ref[tuple(k)])!r}")
         first[b] = _bits(b.t).clone()
     if twice:
         for b in bufs:
