@@ -536,6 +536,60 @@ int mi355_delong_ws_ints(int M, int C, long long n);
 int mi355_delong(const float* scores, const int32_t* labels, int M, int C, long long n, int32_t* ws, long long ws_ints,
                  int64_t* v2, int64_t* pnu, double* var, double* cov, mi355_stream_t s);
 
+/* ---- post-hoc calibration (utils/calibrate.py; nothing in the reference): the temperature of a classifier fitted on held-out
+ * logits (Guo et al. 2017) and the mask threshold of a segmenter with the best mean Dice over a list of candidates ---------- */
+/* Temperature.  x fp32 [N][C] logits, labels int32 [N]; N >= 1, 2 <= C <= 4096, N * C <= 2^26.  With beta = 1 / T the mean NLL
+ *     g(beta) = mean_i(log sum_j exp(beta x_ij - m_i) + m_i - beta x_iy),  m_i = max_j beta x_ij
+ * is convex, g' = mean_i(E_p[x_i] - x_iy), g'' = mean_i Var_p[x_i], p = softmax(beta x_i): evaluated in double relative to the
+ * row maximum, row partials folded in a fixed order.
+ *   mi355_temperature_fit_ws_ints: int32 elements of scratch `ws` (-1 + last_error when the shape is out of range).
+ *   mi355_temperature_fit: a safeguarded Newton iteration on g' over the bracket [2^-6, 2^6], all of it on the device: the host
+ *     enqueues a fixed schedule of 64 (evaluate, update) kernel pairs and never reads beta; once the status is set the
+ *     remaining kernels return at once.  Evaluation 1 is at beta = 1.  Evaluation 2 is at the end of the bracket that g'(1)
+ *     points to (2^6 when g'(1) < 0), which either is the clamp or leaves a bracket with a sign change of g'.  From then on
+ *     the bracket shrinks by the sign of g' and the next beta is beta - g' / g'', replaced by the bracket's geometric mean when
+ *     g'' <= 0 or the step leaves the bracket.  It stops AT the evaluated beta when the step |dbeta| <= 2^-40 beta or
+ *     g' = 0, or after 64 evaluations.
+ *       state double [8] = beta, T = 1 / beta, mean NLL at beta = 1, mean NLL at beta, g'(beta), g''(beta), evaluations, status
+ *       status 0: converged;  1: lower clamp (g' >= 0 at 2^-6), beta = 2^-6;  2: upper clamp (g' <= 0 at 2^6, e.g. separable
+ *         data, where g' underflows to 0), beta = 2^6;  3: flat (g'' = 0 at beta = 1, e.g. every row constant), beta = 1;
+ *         4: the evaluation cap, or g' is a NaN (NaN logits; a label outside 0 .. C - 1 reads nothing and counts as a NaN).
+ *   mi355_temperature_eval: one evaluation at beta_dev[0] (device memory), by the kernels and in the fold order of the fit:
+ *     out double [3] = g, g', g'' — at the fit's beta its state[3..5], bit for bit.  `ws` as for the fit.
+ *   mi355_logits_scale: y[i] = (float)((double)x[i] * beta_dev[0]) over N * C elements (C >= 1), beta read from device memory —
+ *     `state` of the fit — so nothing is read back between fit and apply.  16-byte accesses when x and y are 16-byte aligned.
+ * Threshold sweep.  scores, target fp32 [B][len], thr fp32 [K] STRICTLY ASCENDING (the values live on the device: not checked);
+ * 1 <= B <= 65535, 1 <= len <= 2^24, B * len <= 2^26, 1 <= K <= 1024.  v = scores[b][i], or with is_logit != 0
+ * 1.f / (1.f + __expf(-v)) (mi355_seg_counts' expression); a pixel is positive where target > tthr; its bin is
+ * #{k : v > thr[k]} — strict, as in mi355_seg_counts; a NaN is in bin 0.
+ *   mi355_thr_sweep_chunk: pixels per workgroup; a longer image spans several, whose integer histograms are added.
+ *   mi355_thr_sweep_ws_ints: int32 elements of scratch `ws` (-1 + last_error when the shape is out of range).
+ *   mi355_thr_sweep: tp int32 [B][K], fp int32 [B][K], pos int32 [B]: tp[b][k] = #{positive pixels with v > thr[k]}, fp[b][k]
+ *     the same over the negative pixels, pos[b] the positives.  tp[b][k] is mi355_seg_counts' counts[b][0] at thr[k] when
+ *     tthr = thr[k], tp + fp its counts[b][1].  Exact integers.
+ *   mi355_thr_sweep_fold: per candidate k and image b, in double, with pp = tp + fp and tt = pos:
+ *       Dice = (2 tp + 1e-7) / (pp + tt + 1e-7),  IoU = (tp + 1e-7) / (pp + tt - tp + 1e-7)    (utils/tester.py, without x 100)
+ *     acc double [2][K] (+)= the B images' Dice (row 0) and IoU (row 1) in image order, n_images int64 [1] += B.  The caller
+ *     zeroes both before the first batch: a validation set of many batches accumulates in one fixed order.
+ *   mi355_thr_sweep_pick: out_k int32 [1] = the lowest k with the largest mean Dice acc[0][k] / n_images (0 when nothing was
+ *     folded); out_d double [4] = the mean Dice and mean IoU at out_k, then at k_ref — the candidate equal to the current
+ *     operating point, -1 <= k_ref < K; NaN for -1.
+ * No floating-point atomics (integer LDS atomics in the histogram), no allocation, no sync, no host read-back; bit-reproducible. */
+int mi355_temperature_fit_ws_ints(int N, int C);
+int mi355_temperature_fit(const float* x, int N, int C, const int32_t* labels, int32_t* ws, long long ws_ints, double* state,
+                          mi355_stream_t s);
+int mi355_temperature_eval(const float* x, int N, int C, const int32_t* labels, const double* beta_dev, int32_t* ws,
+                           long long ws_ints, double* out, mi355_stream_t s);
+int mi355_logits_scale(const float* x, int N, int C, const double* beta_dev, float* y, mi355_stream_t s);
+int mi355_thr_sweep_chunk(void);
+int mi355_thr_sweep_ws_ints(int B, long long len, int K);
+int mi355_thr_sweep(const float* scores, const float* target, int B, long long len, const float* thr, int K, int is_logit,
+                    float tthr, int32_t* ws, long long ws_ints, int32_t* tp, int32_t* fp, int32_t* pos, mi355_stream_t s);
+int mi355_thr_sweep_fold(const int32_t* tp, const int32_t* fp, const int32_t* pos, int B, int K, double* acc, int64_t* n_images,
+                         mi355_stream_t s);
+int mi355_thr_sweep_pick(const double* acc, const int64_t* n_images, int K, int k_ref, double* out_d, int32_t* out_k,
+                         mi355_stream_t s);
+
 /* ---- optimiser on flat fp32 buffers (utils/helpers.py:251,304,332-336) ---------------------- */
 /* sumsq partials of a flat gradient buffer; nblocks = mi355_rowreduce_blocks(n). */
 int mi355_sumsq_partial(const float* g, float* partial, long long n, mi355_stream_t s);

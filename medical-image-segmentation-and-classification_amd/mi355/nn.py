@@ -396,6 +396,64 @@ def _cls_calibration(x, labels, bins, is_prob):
     return bin_count, bin_correct, bin_conf, out, scores_t
 
 
+def _temperature_fit(x, labels):
+    """mi355_temperature_fit on a contiguous fp32 device tensor [N, C] and int32 labels [N] -> float64 [8] = beta, T, NLL at beta = 1,
+    NLL at beta, g', g'', evaluations, status (csrc/calibrate.hip).  No host round trip."""
+    N, C = x.shape
+    need = _ws_ints("mi355_temperature_fit_ws_ints", N, C)
+    ws = torch.empty(need, dtype=torch.int32, device=x.device)
+    state = torch.empty(8, dtype=torch.float64, device=x.device)
+    lib.mi355_temperature_fit(x, N, C, labels, ws, need, state)
+    return state
+
+
+def _temperature_eval(x, labels, beta_dev):
+    """mi355_temperature_eval: the mean NLL and its first two derivatives in beta at ``beta_dev[0]`` (float64 device tensor) -> float64 [3]"""
+    N, C = x.shape
+    need = _ws_ints("mi355_temperature_fit_ws_ints", N, C)
+    ws = torch.empty(need, dtype=torch.int32, device=x.device)
+    out = torch.empty(3, dtype=torch.float64, device=x.device)
+    lib.mi355_temperature_eval(x, N, C, labels, beta_dev, ws, need, out)
+    return out
+
+
+def _logits_scale(x, beta_dev):
+    """mi355_logits_scale: fp32 [N, C] times the double at ``beta_dev`` (a float64 device tensor, e.g. _temperature_fit's) -> fp32."""
+    N, C = x.shape
+    y = torch.empty_like(x)
+    lib.mi355_logits_scale(x, N, C, beta_dev, y)
+    return y
+
+
+def _thr_sweep(scores, target, thr, is_logit, target_threshold):
+    """mi355_thr_sweep on contiguous fp32 device tensors [B, len], [B, len] and ascending candidates [K] -> (tp int32 [B, K],
+    fp int32 [B, K], pos int32 [B]).  No host round trip."""
+    B, n = scores.shape
+    K = thr.shape[0]
+    need = _ws_ints("mi355_thr_sweep_ws_ints", B, n, K)
+    dev = scores.device
+    ws = torch.empty(need, dtype=torch.int32, device=dev)
+    tp = torch.empty(B, K, dtype=torch.int32, device=dev)
+    fp = torch.empty(B, K, dtype=torch.int32, device=dev)
+    pos = torch.empty(B, dtype=torch.int32, device=dev)
+    lib.mi355_thr_sweep(scores, target, B, n, thr, K, 1 if is_logit else 0, float(target_threshold), ws, need, tp, fp, pos)
+    return tp, fp, pos
+
+
+def _thr_sweep_fold(tp, fp, pos, acc, n_images):
+    """mi355_thr_sweep_fold: adds a batch's per-image Dice / IoU to ``acc`` (float64 [2, K]) and its size to ``n_images`` (int64 [1])."""
+    B, K = tp.shape
+    lib.mi355_thr_sweep_fold(tp, fp, pos, B, K, acc, n_images)
+
+
+def _thr_sweep_pick(acc, n_images, k_ref):
+    """mi355_thr_sweep_pick -> (float64 [4] = mean Dice, mean IoU at the pick, then at candidate k_ref; int32 [1] = the pick)."""
+    out_d = torch.empty(4, dtype=torch.float64, device=acc.device)
+    out_k = torch.empty(1, dtype=torch.int32, device=acc.device)
+    lib.mi355_thr_sweep_pick(acc, n_images, acc.shape[1], int(k_ref), out_d, out_k)
+    return out_d, out_k
+
+
 class _RegionLovaszFn(torch.autograd.Function):
     """region + Lovasz hinge as ONE autograd node, for the reason documented on _RegionBoundaryFn: every mi355 criterion's backward
     returns the plan's ``dout`` buffer, so the regional backward writes ``dz`` and the Lovasz backward accumulates into it.

@@ -18,27 +18,47 @@ values the models were trained with (trainer.py --clahe-clip / --clahe-grid); th
 result gains a per-pixel uncertainty map and the views' agreement, and the analysis text says how stable the highlighted area is.
 ``sliding=(tile, overlap, weighting)`` (utils/sliding.py): the kept samples are segmented at the resolution of ``predict``'s ``x_seg``
 (``seg_size`` in ``process_files`` / ``process_images``) by overlapping windows of ``tile`` pixels blended on the GPU; the masks come
-back at that resolution, with a map of how far overlapping windows disagree.  The classifier's path is unchanged."""
+back at that resolution, with a map of how far overlapping windows disagree.  The classifier's path is unchanged.
+``calibration=(cls_cal, seg_cal)`` (utils/calibrate.py, fitted by trainer.py --calibrate): the confidence comes from the
+temperature-scaled logits and every mask is cut at the fitted threshold instead of 0.5; the analysis text says so in one sentence."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
+from mi355 import nn as mnn
 from mi355.lib import lib
 
 CLASSES = ["COVID", "Healthy", "Non-COVID"]          # pipeline.py:22
 
 
 class _KeywordOptions(type):
-    """``JointPipeline(..., tta=None, tta_merge="prob", sliding=None, seg_size=None)``: the options are keywords of the call, set
+    """``JointPipeline(..., tta=None, tta_merge="prob", sliding=None, seg_size=None, calibration=None)``: the options are keywords of the call, set
     through their properties once ``__init__`` has run, so ``__init__`` keeps the positional parameter list its callers rely on."""
 
-    def __call__(cls, *args, tta=None, tta_merge="prob", sliding=None, seg_size=None, **kwargs):
+    def __call__(cls, *args, tta=None, tta_merge="prob", sliding=None, seg_size=None, calibration=None, **kwargs):
         self = super().__call__(*args, **kwargs)
+        self.calibration = calibration
         self.tta_merge = tta_merge
         self.tta = tta
         self.sliding = sliding
         self.seg_size = seg_size
         return self
+
+
+class _TemperatureScaled:
+    """a classifier whose logits are multiplied by the double at ``beta`` on the device (mi355_logits_scale): what TTAClassifier is
+    handed when the pipeline is calibrated"""
+
+    def __init__(self, model, beta):
+        self.model, self.beta = model, beta
+
+    @property
+    def training(self):
+        return self.model.training
+
+    def __call__(self, x):
+        return mnn._logits_scale(self.model(x).float().contiguous(), self.beta)
 
 
 class JointPipeline(metaclass=_KeywordOptions):
@@ -51,6 +71,7 @@ class JointPipeline(metaclass=_KeywordOptions):
         self.bucket = int(bucket)
         self.postprocess = postprocess
         self._clahe = None
+        self._calibration, self._beta, self._thr = None, None, 0.5
         self.classification_model = classification_model.to(self.device).eval()
         self.segmentation_model = None if segmentation_model is None else segmentation_model.to(self.device).eval()
 
@@ -69,6 +90,34 @@ class JointPipeline(metaclass=_KeywordOptions):
         if len(value) != 2:
             raise ValueError(f"clahe must be None or (clip, grid), got {value!r}")
         self._clahe = check_clahe(*value)
+
+    @property
+    def calibration(self):
+        """None (default: the softmax as it is, masks cut at 0.5) or (cls_cal, seg_cal), two ``utils.calibrate.Calibration`` — either
+        may be None: the classifier's logits are divided by cls_cal's temperature before the decision, so ``confidence`` is the
+        calibrated one (the class is the same), and seg_cal's threshold takes the place of 0.5 wherever a mask is cut."""
+        return self._calibration
+
+    @calibration.setter
+    def calibration(self, value):
+        if value is None:
+            self._calibration, self._beta, self._thr = None, None, 0.5
+            return
+        if len(value) != 2:
+            raise ValueError(f"calibration must be None or (cls_cal, seg_cal), got {value!r}")
+        cls_cal, seg_cal = value
+        if (cls_cal is not None and cls_cal.kind != "classification") or (seg_cal is not None and seg_cal.kind != "segmentation"):
+            raise ValueError("calibration: (a classification Calibration or None, a segmentation Calibration or None) expected")
+        if cls_cal is not None and not cls_cal.temperature > 0:
+            raise ValueError(f"calibration: temperature > 0 required, got {cls_cal.temperature}")
+        self._beta = None if cls_cal is None else torch.tensor([1.0 / cls_cal.temperature], dtype=torch.float64, device=self.device)
+        self._thr = 0.5 if seg_cal is None else float(np.float32(seg_cal.threshold))
+        self._calibration = (cls_cal, seg_cal)
+        self._sw = None                            # (the window segmenter holds the threshold)
+
+    def _clean(self, masks):
+        """the postprocess on 0 / 255 masks: against the calibrated threshold when there is one (the same cut for any value in (0, 255))"""
+        return self.postprocess(masks) if self._calibration is None else self.postprocess(masks, threshold=self._thr)
 
     @property
     def tta(self):
@@ -170,6 +219,8 @@ class JointPipeline(metaclass=_KeywordOptions):
             logits = cams["logits"].float().contiguous()
         else:
             logits = self.classification_model(x).float().contiguous()
+        if self._beta is not None:
+            logits = mnn._logits_scale(logits, self._beta)
         pred = torch.empty(B, dtype=torch.int32, device=self.device)
         conf = torch.empty(B, dtype=torch.float32, device=self.device)
         kept = torch.empty(B + self.bucket, dtype=torch.int32, device=self.device)
@@ -194,14 +245,14 @@ class JointPipeline(metaclass=_KeywordOptions):
             z = self.segmentation_model(xs)
             if z.dim() == 3:
                 z = z.unsqueeze(1)
-            lib.mi355_mask_scatter(z.float().contiguous(), kept, n, H * W, 0.5, masks)
+            lib.mi355_mask_scatter(z.float().contiguous(), kept, n, H * W, self._thr, masks)
         elif self.segmentation_model is None:
             segmented = torch.zeros_like(segmented)
         out = {"pred": pred, "confidence": conf, "masks": masks, "segmented": segmented}
         if seam is not None:
             out["seam_spread"] = seam
         if self.postprocess is not None:
-            clean = self.postprocess(masks)            # 0 / 255 against 0.5; rows without a segmentation are empty and stay so
+            clean = self._clean(masks)                 # 0 / 255 against 0.5; rows without a segmentation are empty and stay so
             out.update(masks=clean["mask"], masks_raw=masks, n_lesions=clean["n_kept"], area_percent=clean["area_percent"],
                        lesions=clean["out_c"])
         if cams is not None:
@@ -215,14 +266,15 @@ class JointPipeline(metaclass=_KeywordOptions):
         key = (self.sliding, self.bucket, self.segmentation_model)
         if self._sw is None or self._sw[0] != key[:2] or self._sw[1] is not key[2]:
             tile, overlap, weighting = self.sliding
-            self._sw = (key[:2], key[2], SlidingWindowSegmenter(key[2], tile, overlap, weighting, "logit", 0.5, self.bucket))
+            self._sw = (key[:2], key[2], SlidingWindowSegmenter(key[2], tile, overlap, weighting, "logit", self._thr, self.bucket))
         return self._sw[2]
 
     def _predict_tta(self, x):
         """predict() with test-time augmentation: the same steps, every model call replaced by its K views and their merge"""
         from utils.tta import TTAClassifier, fold_views, view_logits
         B, _, H, W = x.shape
-        c = TTAClassifier(self.classification_model, self.tta, keep_class=self.keep, pad=self.bucket)(x)
+        classifier = self.classification_model if self._beta is None else _TemperatureScaled(self.classification_model, self._beta)
+        c = TTAClassifier(classifier, self.tta, keep_class=self.keep, pad=self.bucket)(x)
         pred, kept = c["pred"], c["kept"]
         masks = torch.zeros(B, H, W, dtype=torch.uint8, device=self.device)
         uncertainty = torch.zeros(B, H, W, dtype=torch.float32, device=self.device)
@@ -236,7 +288,7 @@ class JointPipeline(metaclass=_KeywordOptions):
                 kept[n:npad] = kept[0]                 # padding rows repeat a kept sample; their output is dropped
             xs = torch.empty(npad, 3, H, W, dtype=torch.float32, device=self.device)
             lib.mi355_gather_rows(x, kept, npad, 3 * H * W, xs)
-            f = fold_views(view_logits(self.segmentation_model, xs, self.tta, rows=n), self.tta, self.tta_merge, 0.5, kept, masks)
+            f = fold_views(view_logits(self.segmentation_model, xs, self.tta, rows=n), self.tta, self.tta_merge, self._thr, kept, masks)
             rows = kept[:n].long()
             uncertainty[rows] = f["var"]
             same = (f["votes"] == 0) | (f["votes"] == f["valid"])
@@ -245,7 +297,7 @@ class JointPipeline(metaclass=_KeywordOptions):
         out = {"pred": pred, "confidence": c["confidence"], "masks": masks, "segmented": segmented, "agreement": c["agreement"],
                "uncertainty": uncertainty, "stable_percent": stable}
         if self.postprocess is not None:
-            clean = self.postprocess(masks)
+            clean = self._clean(masks)
             out.update(masks=clean["mask"], masks_raw=masks, n_lesions=clean["n_kept"], area_percent=clean["area_percent"],
                        lesions=clean["out_c"])
         if same is not None:                          # over the masks that are returned and overlaid: the cleaned ones with a postprocess
@@ -321,6 +373,12 @@ class JointPipeline(metaclass=_KeywordOptions):
         lesions = (r["n_lesions"].cpu(), r["area_percent"].cpu()) if "n_lesions" in r else None
         stable = r["stable_percent"].cpu() if "stable_percent" in r else None
         positive = self.classes[self.keep]
+        cal_line = ""
+        if self._calibration is not None:
+            cls_cal, seg_cal = self._calibration
+            parts = ([f"confidence at temperature {cls_cal.temperature:.3f}"] if cls_cal is not None else []) \
+                + ([f"mask threshold {self._thr:.4f}"] if seg_cal is not None else [])
+            cal_line = "Calibrated on the validation set: " + " and ".join(parts) + ".\n" if parts else ""
         results = [None] * len(paths)
         row = 0
         for idx, im in zip(order, imgs):
@@ -333,6 +391,7 @@ class JointPipeline(metaclass=_KeywordOptions):
                 prediction, confidence = self.classes[int(pred[row + j])], float(conf[row + j])
                 output_img = None
                 text = f"Diagnosis: {prediction}\nConfidence: {confidence:.2f}%\n"
+                text += cal_line
                 if prediction != positive:
                     text += ("\nRecommendation: Consult a medical professional for final diagnosis. The model suggests no severe "
                              "COVID-19 pathology.")

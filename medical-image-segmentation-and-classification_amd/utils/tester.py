@@ -251,7 +251,8 @@ def test_classification_model(model, test_loader, device, model_name, tta=None, 
     return evaluate_classification_model(model, test_loader, device, model_name, tta=tta, auc=auc, calibration_bins=calibration_bins)
 
 
-def evaluate_classification_model(model, test_loader, device, model_name, tta=None, auc=False, calibration_bins=15, ci=None):
+def evaluate_classification_model(model, test_loader, device, model_name, tta=None, auc=False, calibration_bins=15, ci=None,
+                                  calibration=None):
     """``tta`` (a preset name or a list of views, utils/tta.py; or pass ``utils.tta.TTAClassifier(model, views)`` as the model): the
     predictions are the argmax of the views' mean softmax, and the result gains ``tta_agreement`` (%, the mean share of views whose
     own argmax is the prediction) and ``tta_views``.
@@ -265,9 +266,18 @@ def evaluate_classification_model(model, test_loader, device, model_name, tta=No
     interval call, one read-back).  The result gains ``<key>_ci`` = (lo, hi) and ``<key>_se`` for accuracy, precision, recall, f1
     and, with ``auc``, auroc and average_precision; ``auroc_ci_per_class`` / ``auroc_se_per_class``; ``auroc_delong_ci_per_class``
     (auc -+ z sqrt(DeLong's variance), clipped to [0, 1]); ``ci_detail`` ({name: point, mean, se, lo, hi, valid}: ``point`` is the
-    same code on the identity resample) and ``ci_replicates`` / ``ci_level`` / ``ci_seed``; every printed figure its `` [lo, hi]``."""
+    same code on the identity resample) and ``ci_replicates`` / ``ci_level`` / ``ci_seed``; every printed figure its `` [lo, hi]``.
+    ``calibration`` (a ``utils.calibrate.Calibration`` of kind "classification", trainer.py --calibrate): with ``auc`` the logits are
+    divided by its temperature (csrc/calibrate.hip) before the softmax that feeds the calibration and ranking figures, so ``ece``,
+    ``brier`` and ``nll`` are the calibrated model's — ``nll`` evaluated in double on the unrounded scaled logits, the figure the fit
+    minimised; the argmax, and with it the accuracy and the confusion matrix, is unchanged.  The result gains ``temperature`` and one
+    line is printed.  Not together with ``tta``, whose scores are mean probabilities: ValueError."""
     from utils.tta import TTAClassifier
     ci = _check_ci(ci)
+    if calibration is not None and calibration.kind != "classification":
+        raise ValueError(f"a classifier's calibration is expected, got one of kind {calibration.kind!r}")
+    if calibration is not None and (tta is not None or isinstance(model, TTAClassifier)):
+        raise ValueError("a temperature scales logits: calibration together with tta (mean probabilities) is not supported")
     model.eval()
     preds, labels, agree, kept_scores = [], [], [], []
     print(f"\n{'=' * 60}\nTesting Classification Model: {model_name}\n{'=' * 60}")
@@ -296,15 +306,24 @@ def evaluate_classification_model(model, test_loader, device, model_name, tta=No
         m["tta_views"] = len(cls_tta.views)
         m["tta_agreement"] = float(torch.cat(agree).double().mean().cpu()) / m["tta_views"] * 100
     if auc:
-        from utils.ranking import calibration, rank_metrics
+        from utils.ranking import calibration as calibration_figures, rank_metrics
         y = torch.cat(labels).to(torch.int32)
-        cal = calibration(torch.cat(kept_scores), y, bins=calibration_bins, is_prob=tta is not None)
+        scores = torch.cat(kept_scores)
+        if calibration is not None:
+            from utils.calibrate import apply_temperature, nll_at
+            nll_cal = nll_at(scores, y, calibration)
+            scores = apply_temperature(scores, calibration)
+        cal = calibration_figures(scores, y, bins=calibration_bins, is_prob=tta is not None)
         rk = rank_metrics(cal["scores_t"], labels=y)
         m["auroc_per_class"] = rk["auroc"].cpu().numpy()
         m["ap_per_class"] = rk["average_precision"].cpu().numpy()
         m["auroc"], m["auc_classes"] = _nanmean(m["auroc_per_class"])
         m["average_precision"] = _nanmean(m["ap_per_class"])[0]
         m["ece"], m["brier"], m["nll"] = float(cal["ece"].cpu()), float(cal["brier"].cpu()), float(cal["nll"].cpu())
+        if calibration is not None:
+            m["nll"] = float(nll_cal.cpu())
+    if calibration is not None:
+        m["temperature"] = float(calibration.temperature)
     d = None
     if ci is not None:
         from statistics import NormalDist
@@ -347,6 +366,8 @@ def evaluate_classification_model(model, test_loader, device, model_name, tta=No
         print(f"AUROC / AP: {m['auroc']:.4f}{_ci_text(d, 'auroc', '.4f')} / {m['average_precision']:.4f}{_ci_text(d, 'average_precision', '.4f')}"
               f" (macro, one-vs-rest, {m['auc_classes']} classes)")
         print(f"ECE ({calibration_bins} bins) / Brier / NLL: {m['ece']:.4f} / {m['brier']:.4f} / {m['nll']:.4f}")
+    if calibration is not None:
+        print(f"Calibration: {calibration.describe()}")
     print("\nPer-Class Metrics:")
     for i, c in enumerate(CLASSES[:len(m["f1_per_class"])]):   # (the reference indexes all of CLASSES, tester.py:282-296, and dies when a class is absent)
         delong_text = ""
@@ -378,7 +399,7 @@ def evaluate_segmentation_model(model, test_loader, device, model_name, surface=
     return evaluate_segmentation_model_ci(model, test_loader, device, model_name, surface=surface, auc=auc)
 
 
-def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surface=False, auc=False, ci=None):
+def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surface=False, auc=False, ci=None, calibration=None):
     """``surface=True`` adds hausdorff, hd95, assd (pixels; mean over the samples where both masks have a border), surface_dice
     (%, tolerance 2 pixels) and surface_samples (how many samples entered those means) behind the six overlap metrics.
     Test-time augmentation: pass ``utils.tta.TTASegmenter(model, views, merge)`` as the model.  Every metric is then taken from the
@@ -400,13 +421,19 @@ def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surfa
     once as [M, n] doubles and their NaN-aware means are bootstrapped over the images (utils/resample.py).  The result gains
     ``<key>_ci`` = (lo, hi) and ``<key>_se`` for each of them, ``ci_detail`` ({key: point, mean, se, lo, hi, valid}; ``point`` is the
     same fold on the identity resample, equal to the plain figure up to the order of the additions) and ``ci_replicates`` /
-    ``ci_level`` / ``ci_seed``; every printed figure its `` [lo, hi]``."""
+    ``ci_level`` / ``ci_seed``; every printed figure its `` [lo, hi]``.
+    ``calibration`` (a ``utils.calibrate.Calibration`` of kind "segmentation", trainer.py --calibrate): its threshold takes the place
+    of 0.5 in the overlap counters and the surface metrics (the binary masks of the loaders are the same under either); the result
+    gains ``threshold`` and one line is printed.  Hand a TTASegmenter / SlidingWindowSegmenter the same ``thr``."""
     from utils.sliding import SlidingWindowSegmenter
     from utils.tta import TTASegmenter
     ci = _check_ci(ci)
     model.eval()
     tta = seg_tta = model if isinstance(model, TTASegmenter) else None
     sw = model if isinstance(model, SlidingWindowSegmenter) else None
+    if calibration is not None and calibration.kind != "segmentation":
+        raise ValueError(f"a segmenter's calibration is expected, got one of kind {calibration.kind!r}")
+    thr = 0.5 if calibration is None else float(np.float32(calibration.threshold))
     is_logit = True                               # the model's output; with tta the merged map, a probability unless merge="logit"
     if tta is not None:
         tta_merge = seg_tta.merge
@@ -440,8 +467,8 @@ def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surfa
             masks = masks.to(device)
             B, per = out.shape[0], out[0].numel()
             cnt = torch.empty(B, 4, dtype=torch.float32, device=out.device)
-            lib.mi355_seg_counts(out.float().contiguous(), masks.float().contiguous(), cnt, B, per, 1 if is_logit else 0, 0.5)
-            pending.append((cnt, per, _surface_raw(out, masks, is_logit, 0.5, 95, 4) if surface else None))
+            lib.mi355_seg_counts(out.float().contiguous(), masks.float().contiguous(), cnt, B, per, 1 if is_logit else 0, thr)
+            pending.append((cnt, per, _surface_raw(out, masks, is_logit, thr, 95, 4) if surface else None))
             if auc:
                 rk = rank_metrics(out.float().reshape(B, per), target=masks.float().reshape(B, per), threshold=0.5)
                 ranked.append((rk["auroc"], rk["average_precision"]))
@@ -494,6 +521,8 @@ def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surfa
     if sw is not None:
         avg["sw_tiles"] = int(sw_tiles)
         avg["sw_seam_spread"] = float(seam.mean())
+    if calibration is not None:
+        avg["threshold"] = thr
     print(f"\n{model_name} Test Results:\n{'-' * 60}")
     b = lambda key, fmt=".2f": _ci_text(d, key, fmt)      # noqa: E731  ('' without ci)
     print(f"IoU (Jaccard):     {avg['iou']:.2f}%{b('iou')}\nDice Coefficient:  {avg['dice']:.2f}%{b('dice')}\n"
@@ -508,6 +537,7 @@ def evaluate_segmentation_model_ci(model, test_loader, device, model_name, surfa
           + (f"\nTTA unanimous:     {avg['tta_unanimous']:.2f}% of the pixels ({avg['tta_views']} views, merged {tta_merge})" if tta is not None else "")
           + (f"\nSliding window:    {avg['sw_tiles']} tiles of {sw.tile} px per image (overlap {sw.overlap:g}, {sw.weighting} weights, merged "
              f"{sw.merge}), seam spread {avg['sw_seam_spread']:.4f}" if sw is not None else "")
+          + (f"\nCalibration:       {calibration.describe()}" if calibration is not None else "")
           + (f"\n{ci.footer()}" if ci is not None else "")
           + f"\n{'=' * 60}\n")
     return avg
@@ -521,8 +551,8 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
 
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
-                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, ci=None, auc=False,
-                    calibration_bins=15, surface=False):
+                    seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, ci=None, calibration=None,
+                    auc=False, calibration_bins=15, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -541,7 +571,12 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     point of the option is a ``size`` above the training size with ``tile`` at the training size.  ``sliding`` together with ``tta``: ValueError.
     ``ci`` (a ``CI``, the number of bootstrap replicates, or (replicates, level, seed)): every figure of every model gets its
     bootstrap interval (the ``ci`` of the two loops).  All models share the seed, hence the resamples, and what ``print_paired_tests``
-    needs stays on the device in ``ci.kept`` — pass a ``CI`` to have it afterwards."""
+    needs stays on the device in ``ci.kept`` — pass a ``CI`` to have it afterwards.
+    ``calibration`` (a directory): every model that is tested is given its sidecar ``{name}_calibration.json`` (utils/calibrate.py,
+    written by trainer.py --calibrate) from that directory or its ``classification_models`` / ``segmentation_models`` sub-directory:
+    the classifiers' temperature (with ``auc``: their ECE, Brier score and NLL are the calibrated ones; not together with ``tta``),
+    the segmenters' threshold in place of 0.5 (also in the TTA and sliding-window folds).  A checkpoint without a sidecar:
+    FileNotFoundError naming the file."""
     from utils.helpers import get_class_model, get_seg_model
     ci = _check_ci(ci)
     size = IMG_SIZE if size is None else int(size)
@@ -566,6 +601,7 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     cls_weights_dir = CLS_WEIGHTS_DIR if cls_weights_dir is None else cls_weights_dir
     seg_weights_dir = SEG_WEIGHTS_DIR if seg_weights_dir is None else seg_weights_dir
     results = {}
+    cals = {}                                     # model name -> its Calibration (calibration is a directory)
 
     def run(files, wdir, loader, build, test, n_samples_label):
         print(f"\n[INFO] {n_samples_label} Test Dataset: {len(loader.dataset)} samples")
@@ -578,6 +614,9 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             if model_name in ("CLIP", "CLIPSeg"):
                 print(f"\n[WARNING] {model_name} is a hub model outside the MI355X conv path; skipping {weight_path}")
                 continue
+            if calibration is not None:
+                from utils.calibrate import find_sidecar
+                cals[model_name] = find_sidecar(calibration, model_name, n_samples_label.lower() + "_models")
             try:
                 model = build(model_name)
                 model.load_state_dict(torch.load(weight_path, map_location=device))
@@ -617,6 +656,8 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             cls_test = lambda m, l, d, name: test_classification_model(m, l, d, name, tta=tta, auc=True, calibration_bins=calibration_bins)  # noqa: E731
         if ci is not None:
             cls_test = lambda m, l, d, name: evaluate_classification_model(m, l, d, name, tta=tta, auc=auc, calibration_bins=calibration_bins, ci=ci)  # noqa: E731
+        if calibration is not None:
+            cls_test = lambda m, l, d, name: evaluate_classification_model(m, l, d, name, tta=tta, auc=auc, calibration_bins=calibration_bins, ci=ci, calibration=cals[name])  # noqa: E731
         run(_CLS_FILES, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], cls_test, "Classification")
     if seg_loader is None:
         print(f"\n[WARNING] Segmentation test dataset not found: no loader given for {DATA_ROOT!r}")
@@ -644,6 +685,14 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             else:
                 seg_wrap = lambda m: m  # noqa: E731
             seg_test = lambda m, l, d, name: evaluate_segmentation_model_ci(seg_wrap(m), l, d, name, surface=surface, auc=auc, ci=ci)  # noqa: E731
+        if calibration is not None:
+            def seg_test(m, l, d, name):
+                t = float(np.float32(cals[name].threshold))
+                if sliding is not None:
+                    m = SlidingWindowSegmenter(m, sliding[0], sliding[1], sliding[2], thr=t, batch=sw_batch)
+                elif tta is not None:
+                    m = TTASegmenter(m, tta, tta_merge, t)
+                return evaluate_segmentation_model_ci(m, l, d, name, surface=surface, auc=auc, ci=ci, calibration=cals[name])
         run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
     return results
 
@@ -817,6 +866,9 @@ def build_parser():
     _ap.add_argument("--auc", action="store_true",
                      help="also report ROC-AUC and average precision (per class / per image over the pixels) and the classifiers' ECE, Brier score and NLL")
     _ap.add_argument("--calibration-bins", type=int, default=15, help="--auc: confidence bins of the expected calibration error")
+    _ap.add_argument("--calibration", default=None, metavar="DIR",
+                     help="apply the post-hoc calibration fitted by trainer.py --calibrate: DIR holds the {name}_calibration.json sidecars "
+                          "(or the classification_models / segmentation_models directories that do)")
     _ap.add_argument("--ci", type=int, default=0,
                      help="bootstrap replicates (up to 8192) for a percentile interval on every figure and paired tests between the models; 0 = off")
     _ap.add_argument("--ci-level", type=float, default=0.95, help="--ci: the level of the intervals")
@@ -847,6 +899,8 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
         _kw["size"] = _args.size
     if _args.ci != 0:
         _kw["ci"] = CI(_args.ci, _args.ci_level, _args.ci_seed)
+    if _args.calibration is not None:
+        _kw["calibration"] = _args.calibration
     results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
     if _args.ci != 0:

@@ -105,7 +105,25 @@ def build_parser():
     ap.add_argument("--mix-per-sample", action="store_true", help="mixup / CutMix: a draw per sample (default: one per batch)")
     ap.add_argument("--class-weight", choices=["none", "balanced"], default="none",
                     help="cls: per-class loss weights n / (C * count_c) from the training files (--data-root; ignored for synthetic data)")
+    ap.add_argument("--calibrate", action="store_true",
+                    help="after training, fit the post-hoc calibration of the best checkpoint on the validation split (utils/calibrate.py): "
+                         "a classifier's temperature, a segmenter's Dice-optimal mask threshold; written next to the checkpoint as "
+                         "{name}_calibration.json for tester.py --calibration and JointPipeline(calibration=...)")
     return ap
+
+
+def calibrate_checkpoint(model, val_dl, device, name, save_dir, seg, say=print):
+    """--calibrate: reload ``name``'s best checkpoint from ``save_dir`` into ``model``, fit its calibration on ``val_dl`` (rank 0; the
+    other ranks skip) and write the sidecar next to the checkpoint -> the Calibration, or None on the other ranks."""
+    from utils.calibrate import Calibration, calibrate_model
+    from utils.distributed import dist_info
+    if dist_info()[0] != 0:
+        return None
+    model.load_state_dict(torch.load(os.path.join(save_dir, f"{name}_best_loss.pt" if seg else f"{name}_best_acc.pt"), map_location=device))
+    cal = calibrate_model(model.to(device), val_dl, device, seg)
+    path = cal.save(Calibration.path(save_dir, name))
+    say(f"[calibration] {name}: {cal.describe()} -> {path}")
+    return cal
 
 
 def elastic_arg(args):
@@ -273,10 +291,14 @@ def main():
                 model, head = get_class_model(name)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "classification_models"),
                              seg=False, cls_head_name=head, criterion=cls_crit)
+                if args.calibrate:
+                    calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "classification_models"), False, say)
             else:
                 model = get_seg_model(name)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True,
                              criterion=seg_criterion(args))
+                if args.calibrate:
+                    calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "segmentation_models"), True, say)
             results[(task, name)] = best
     say("\n===== SUMMARY =====")
     for (task, name), best in results.items():
