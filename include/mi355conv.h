@@ -386,6 +386,46 @@ int mi355_seg_loss_fwd(const float* z, const float* t, int B, long long per, flo
                        float smooth, int per_sample, float* partial, float* state, float* loss, mi355_stream_t s);
 int mi355_seg_loss_bwd(const float* z, const float* t, int B, long long per, float bce_weight, const float* state,
                        const float* gscale, float* dz, mi355_stream_t s);
+/* Multi-class segmentation (nothing in the reference, whose losses and metrics are binary): per-pixel softmax cross-entropy +
+ * per-class soft Dice, and the argmax / confusion-matrix pass of the metrics.  Logits z fp32 [N][C][HW] (the NCHW map of the
+ * K-channel heads; a plan's dout has the same layout), labels y uint8 [N][HW], 2 <= C <= 16, N <= 65535, HW <= 2^30.
+ * ignore_index is -1 (none) or in [C, 255]; a pixel is valid when its label is in [0, C), and EVERY label >= C is ignored, whether
+ * or not it equals ignore_index: nothing is indexed by it.  weight fp32 [C] on the device or NULL (all ones); the weights must not
+ * be negative (device memory: not checked).  With p = softmax_c(z) at each pixel, sums over the valid pixels:
+ *   CE     = sum w[y] (logsumexp(z) - z_y) / sum w[y]: torch.nn.functional.cross_entropy(z, y, weight, ignore_index) with
+ *            class-index targets and its weighted-mean normalisation, EXCEPT that with sum w[y] = 0 (no valid pixel) CE and
+ *            its gradient are 0 where torch returns NaN.  No label smoothing.
+ *   dice_c = (2 I_c + smooth) / (P_c + T_c + smooth),  I_c = sum p_c [y = c],  P_c = sum p_c,  T_c = sum [y = c], the sums
+ *            over the whole batch (per_sample = 0) or per image (per_sample = 1)
+ *   Dice   = 1 - mean_{c in S} dice_c (per_sample: the mean over images of that); S = every class, or c >= 1 with
+ *            include_background = 0; a class absent from the targets stays in the mean (the reference DiceLoss rule per class)
+ *   loss[0] = ce_weight CE + dice_weight Dice,  loss[1] = CE,  loss[2] = Dice
+ *   dz_k   = gscale[0] (ce_weight w[y] (p_k - [y = k]) / sum w + dice_weight p_k (g_k - sum_c g_c p_c)) at valid pixels, exactly
+ *            +0.f at ignored ones; g_c = -(a_c [y = c] - b_c) [c in S] / |S| (/ N with per_sample), a_c = 2 / den_c,
+ *            b_c = (2 I_c + smooth) / den_c^2, den_c = P_c + T_c + smooth.
+ * Inputs are widened to double, exp / log evaluated in double, every sum taken in double in a fixed order, results rounded to
+ * float once on store; no floating-point atomics: the same input gives the same bytes.
+ *   mi355_mcseg_rows:      rows of MI355_MCSEG_ROW doubles `partial` must hold (-1 + last_error when out of range); a function of
+ *     (N, HW) alone.  A workgroup walks chunks of 1024 pixels of one image; rows = N * min(ceil(HW / 1024), max(1, 2048 / N)).
+ *   mi355_mcseg_loss_fwd:  one pass over z and y (16-byte plane loads, four pixels per lane, when HW % 4 == 0, z is 16-byte and
+ *     y 4-byte aligned; one pixel per lane otherwise), a fold of each image's rows (one workgroup per image) and a one-workgroup
+ *     finalize, each in a fixed order; leaves loss[0..3) and `state`, 2 + 2 N C doubles:
+ *     1 / sum w (0 when no pixel is valid), sum w, then per (n, c) the pair (a_c, b_c) [c in S] / |S| (/ N with per_sample).
+ *   mi355_mcseg_loss_bwd:  one pass from the `state` the forward left (same arguments); gscale = upstream gradient x loss scale
+ *     on the device, NULL = 1.  It does not recompute the loss.
+ *   mi355_mcseg_confusion: pred = the first maximum of z over c (v > best in ascending c, starting from -inf and class 0: ties go
+ *     to the lower class, a NaN never wins); conf int32 [N][C][C] is cleared and conf[n][y][pred] counts the valid pixels (integer
+ *     atomics: exact, order-independent); pred uint8 [N][HW] or NULL is written for every pixel, ignored ones included. */
+#define MI355_MCSEG_ROW 50
+int mi355_mcseg_rows(int N, long long HW);
+int mi355_mcseg_loss_fwd(const float* z, const uint8_t* y, int N, int C, long long HW, const float* weight, int ignore_index,
+                         float ce_weight, float dice_weight, float smooth, int per_sample, int include_background,
+                         double* partial, double* state, float* loss, mi355_stream_t s);
+int mi355_mcseg_loss_bwd(const float* z, const uint8_t* y, int N, int C, long long HW, const float* weight, int ignore_index,
+                         float ce_weight, float dice_weight, const double* state, const float* gscale, float* dz,
+                         mi355_stream_t s);
+int mi355_mcseg_confusion(const float* z, const uint8_t* y, int N, int C, long long HW, int ignore_index, int32_t* conf,
+                          uint8_t* pred, mi355_stream_t s);
 /* Boundary loss (Kervadec et al., MIDL 2019; nothing in the reference): the mean of sigmoid(z) * phi, phi the signed
  * Euclidean distance map of the ground truth, rebuilt on the device for every batch.
  *   mi355_signed_dist2: target [B][H][W] fp32, binarised as target > thr -> sd2 int32 [B][H][W]: +min(dy^2 + dx^2) over

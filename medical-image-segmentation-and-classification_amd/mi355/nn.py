@@ -674,3 +674,158 @@ class MixCrossEntropyLoss(nn.Module):
 
     def extra_repr(self):
         return f"label_smoothing={self.label_smoothing}, weight={None if self.weight is None else self.weight.tolist()}"
+
+
+# ---- multi-class segmentation (csrc/mcseg.hip) ---------------------------------------------------------------------------------
+MCSEG_ROW = 50      # MI355_MCSEG_ROW of include/mi355conv.h: doubles per partial row
+
+
+def _mc_labels(target, N, HW):
+    """-> contiguous uint8 [N, HW] labels from a uint8 / integer target [N, H, W] or [N, 1, H, W].  A uint8 target is used as it
+    is; any other integer dtype is converted once, after a range check (one synchronisation: hand over uint8 to avoid it)."""
+    if target.dtype.is_floating_point or target.dtype == torch.bool:
+        raise ValueError(f"class-index labels (uint8 or an integer dtype) expected, got {target.dtype}")
+    if target.numel() != N * HW or target.size(0) != N:
+        raise ValueError(f"target size {tuple(target.shape)} must match the logits' [N, H, W] = {N} x {HW} pixels")
+    if target.dtype != torch.uint8:
+        if target.numel() and (int(target.min()) < 0 or int(target.max()) > 255):
+            raise ValueError(f"labels must lie in [0, 255] (class indices and the ignore value), got [{int(target.min())}, {int(target.max())}]")
+        target = target.to(torch.uint8)
+    return target.contiguous().view(N, HW)
+
+
+def _mc_confusion(out, labels, ignore_index=255, return_pred=False):
+    """mi355_mcseg_confusion on logits [N, C, ...] and labels (see _mc_labels) -> int32 [N, C, C] (and uint8 pred [N, HW]); no sync."""
+    o = out.detach()
+    if o.dtype != torch.float32:
+        o = o.float()
+    if not o.is_contiguous():
+        o = o.contiguous()
+    if o.dim() < 3:
+        raise ValueError(f"logits [N, C, ...] expected, got {tuple(o.shape)}")
+    N, C = o.shape[:2]
+    HW = o.numel() // max(N * C, 1)
+    y = _mc_labels(labels.to(o.device), N, HW)
+    conf = torch.empty(N, C, C, dtype=torch.int32, device=o.device)
+    pred = torch.empty(N, HW, dtype=torch.uint8, device=o.device) if return_pred else None
+    lib.mi355_mcseg_confusion(o, y, N, C, HW, int(ignore_index), conf, pred)
+    return (conf, pred) if return_pred else conf
+
+
+class _MultiClassSegFn(torch.autograd.Function):
+    """Softmax cross-entropy + per-class Dice as ONE node (csrc/mcseg.hip): the forward leaves the three loss terms and the backward's
+    coefficients on the device, the backward is one pass that writes dL/dlogits — into the plan's ``dout`` when there is one."""
+
+    @staticmethod
+    def forward(ctx, out, labels, plan, weight, cfg, terms):
+        o = out.detach()
+        if not o.is_contiguous():
+            o = o.contiguous()
+        N, C = o.shape[:2]
+        HW = o.numel() // (N * C)
+        rows = lib.mi355_mcseg_rows(N, HW)
+        if rows <= 0:
+            raise RuntimeError(f"mi355_mcseg_rows failed: {lib.raw('mi355_last_error')().decode()}")
+        # one fp64 buffer: [rows x MCSEG_ROW partial sums | state 2 + 2 N C]
+        buf = torch.empty(rows * MCSEG_ROW + 2 + 2 * N * C, dtype=torch.float64, device=o.device)
+        partial, state = buf[: rows * MCSEG_ROW], buf[rows * MCSEG_ROW:]
+        loss = torch.empty(3, dtype=torch.float32, device=o.device)
+        ce_w, dice_w, smooth, per_sample, include_bg, ignore = cfg
+        lib.mi355_mcseg_loss_fwd(o, labels, N, C, HW, weight, ignore, ce_w, dice_w, smooth, 1 if per_sample else 0,
+                                 1 if include_bg else 0, partial, state, loss)
+        ctx.o, ctx.y, ctx.plan, ctx.w, ctx.state, ctx.cfg = o, labels, plan, weight, state, cfg
+        terms[:] = [loss[1], loss[2]]             # device views for logging (MultiClassSegLoss.last_terms); not part of the graph
+        return loss[:1].view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, plan = ctx.o, ctx.plan
+        n = o.numel()
+        N, C = o.shape[:2]
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        ce_w, dice_w, _, _, _, ignore = ctx.cfg
+        lib.mi355_mcseg_loss_bwd(o, ctx.y, N, C, n // (N * C), ctx.w, ignore, ce_w, dice_w, ctx.state, gs, dz)
+        return dz[:n].view(o.shape), None, None, None, None, None
+
+
+class MultiClassSegLoss(nn.Module):
+    """ce_weight * softmax cross-entropy + dice_weight * (1 - mean per-class soft Dice) on K-channel logits [N, K, H, W] and a
+    class-index target (uint8 [N, H, W] or [N, 1, H, W]; another integer dtype is range-checked and converted once), on the HIP
+    library.  The cross-entropy is ``F.cross_entropy(out, target, class_weight, ignore_index)`` with its weighted-mean normalisation,
+    except that a batch without a valid pixel gives 0 (and a zero gradient) where torch gives NaN.  The Dice sums run over the batch
+    (``per_sample=False``, the reference DiceLoss rule per class: a class absent from the targets stays in the mean) or per image;
+    ``include_background=False`` leaves class 0 out of the Dice mean.  Every label >= K is ignored, ``ignore_index`` among them.
+    One autograd node: the gradient goes straight into the plan's ``dout`` when the logits come from a mi355 ``Net``.
+    ``last_terms`` = device views (cross-entropy, Dice) of the last forward, for logging without a sync.  Deterministic."""
+
+    def __init__(self, num_classes, ce_weight=1.0, dice_weight=0.0, class_weight=None, ignore_index=255, smooth=1.0, per_sample=False,
+                 include_background=True):
+        super().__init__()
+        num_classes = int(num_classes)
+        if num_classes < 2:
+            raise ValueError(f"num_classes must be >= 2 (got {num_classes}): one foreground is the binary losses' case (CombinedLoss)")
+        if num_classes > 16:
+            raise ValueError(f"num_classes must be <= 16 (got {num_classes})")
+        if ce_weight < 0 or dice_weight < 0 or smooth < 0:
+            raise ValueError(f"ce_weight, dice_weight and smooth must not be negative ({ce_weight}, {dice_weight}, {smooth})")
+        ignore_index = -1 if ignore_index is None else int(ignore_index)
+        if ignore_index != -1 and not num_classes <= ignore_index <= 255:
+            raise ValueError(f"ignore_index must be None / -1 or lie in [{num_classes}, 255] (got {ignore_index})")
+        if class_weight is not None:
+            class_weight = torch.as_tensor(class_weight, dtype=torch.float32).detach().reshape(-1).contiguous().clone()
+            if class_weight.numel() != num_classes or not bool(torch.isfinite(class_weight).all()) or bool((class_weight < 0).any()):
+                raise ValueError(f"class_weight must hold {num_classes} finite values >= 0 ({class_weight.tolist()})")
+        self.register_buffer("class_weight", class_weight)
+        self.num_classes, self.ignore_index = num_classes, ignore_index
+        self.ce_weight, self.dice_weight, self.smooth = float(ce_weight), float(dice_weight), float(smooth)
+        self.per_sample, self.include_background = bool(per_sample), bool(include_background)
+        self.last_terms = None
+
+    def _check(self, out):
+        if out.dim() < 3 or out.shape[1] != self.num_classes:
+            raise ValueError(f"logits [N, {self.num_classes}, H, W] expected, got {tuple(out.shape)}")
+
+    def forward(self, out, target):
+        self._check(out)
+        plan = getattr(out, "_mi355_plan", None)
+        if out.dtype != torch.float32:
+            out = out.float()
+        N, C = out.shape[:2]
+        labels = _mc_labels(target.to(out.device), N, out.numel() // (N * C))
+        w = self.class_weight
+        if w is not None and w.device != out.device:
+            self.class_weight = w = w.to(out.device)
+        cfg = (self.ce_weight, self.dice_weight, self.smooth, self.per_sample, self.include_background, self.ignore_index)
+        terms = []
+        loss = _MultiClassSegFn.apply(out, labels, plan, w, cfg, terms)
+        self.last_terms = tuple(terms)
+        return loss
+
+    def confusion(self, out, target, return_pred=False):
+        """int32 [N, K, K] device tensor, conf[n, label, prediction] over the valid pixels (mi355_mcseg_confusion); no sync."""
+        self._check(out)
+        return _mc_confusion(out, target, self.ignore_index, return_pred)
+
+    def val_metric(self, out, target):
+        """Mean IoU of the batch as a 0-dim device tensor (no sync): tp / (row + col - tp) from the batch-summed confusion matrix,
+        averaged over the classes with a non-zero union (0 when there is none)."""
+        c = self.confusion(out, target).sum(0).to(torch.float32)
+        tp = torch.diagonal(c)
+        union = c.sum(1) + c.sum(0) - tp
+        ok = union > 0
+        iou = torch.where(ok, tp / torch.where(ok, union, torch.ones_like(union)), torch.zeros_like(union))
+        return iou.sum() / ok.sum().clamp(min=1).to(torch.float32)
+
+    def extra_repr(self):
+        return (f"num_classes={self.num_classes}, ce_weight={self.ce_weight}, dice_weight={self.dice_weight}, "
+                f"class_weight={None if self.class_weight is None else self.class_weight.tolist()}, ignore_index={self.ignore_index}, "
+                f"smooth={self.smooth}, per_sample={self.per_sample}, include_background={self.include_background}")
+
+
+class MultiClassDiceLoss(MultiClassSegLoss):
+    """1 - mean per-class soft Dice of softmax(logits): MultiClassSegLoss(num_classes, 0, 1) on the same kernels."""
+
+    def __init__(self, num_classes, class_weight=None, ignore_index=255, smooth=1.0, per_sample=False, include_background=True):
+        super().__init__(num_classes, 0.0, 1.0, class_weight, ignore_index, smooth, per_sample, include_background)

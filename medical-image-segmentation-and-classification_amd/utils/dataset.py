@@ -97,8 +97,13 @@ class ClassificationDataset:
 class SegmentationDataset:
     is_seg = True
 
-    def __init__(self, root, transform, split="train"):
-        self.root, self.transform = root, transform
+    def __init__(self, root, transform, split="train", labels=False):
+        """``labels=True`` (multi-class segmentation): the mask PNG's grey value is the class index and 255 is ignore; without a
+        transform the mask then comes back as the uint8 label map [H, W] instead of the float {0, 1} map [1, H, W].  Pair it with
+        ``SegBatchTransform(labels=True)``."""
+        self.root, self.transform, self.labels = root, transform, bool(labels)
+        if transform is not None and bool(getattr(transform, "labels", False)) != self.labels:
+            raise ValueError(f"labels={self.labels} but the transform was built with labels={getattr(transform, 'labels', False)}")
         self.pairs = []
         for img_id, cls in _rows(root, split):
             ip = os.path.join(root, cls, "images", f"{img_id}.png")
@@ -117,6 +122,8 @@ class SegmentationDataset:
 
     def __getitem__(self, idx):
         img, mask = self.load_batch([idx], 1)
+        if self.transform is None and self.labels:
+            return img[0].permute(2, 0, 1), mask[0]
         if self.transform is None:
             return img[0].permute(2, 0, 1), mask[0][None].float() / 255.0   # dataset.py:129-133
         x, y = self.transform(img, mask)

@@ -56,10 +56,14 @@ class SegBatchTransform:
     [N,Hs,Ws]) -> (x float32 [N,3,S,S] normalised, y float32 [N,1,S,S] in {0,1})`` on the GPU.  ``params`` fixes the draws of a
     train-mode call: ``(mats, bcs)`` as ``draw`` returns them, plus, with ``elastic=(alpha, sigma, p)``, an optional third element
     ``(noise [N,2,S,S], alphas [N])`` as ``draw_elastic`` returns it.  ``clahe=(clip, grid)`` equalises the resized image (not the mask)
-    in both modes."""
+    in both modes.  ``labels=True`` (multi-class segmentation: the mask's grey value is the class index, 255 = ignore): the mask
+    comes back as the warped uint8 label map ``[N,S,S]`` — it went through the nearest-neighbour path of the same warps, so labels
+    survive resize, ShiftScaleRotate, flip and elastic unmixed; pixels the warp pulls in from outside the image are 0 (background) —
+    and the final ``/ 255`` is skipped.  ``labels=False``: every launch, draw and byte of a batch as before."""
 
-    def __init__(self, size=256, train=False, seed=0, device="cuda", elastic=None, clahe=None):
+    def __init__(self, size=256, train=False, seed=0, device="cuda", elastic=None, clahe=None, labels=False):
         self.size, self.train, self.device = size, train, torch.device(device)
+        self.labels = bool(labels)
         self.gen = torch.Generator().manual_seed(seed)
         self.elastic = None
         if elastic is not None:
@@ -154,6 +158,8 @@ class SegBatchTransform:
         lib.mi355_normalize_u8(img, n, s, s, 3, bc, self.mean, self.std, x)
         if msk is None:
             return x
+        if self.labels:
+            return x, msk.view(n, s, s)
         y = torch.empty(n, 1, s, s, dtype=torch.float32, device=self.device)
         lib.mi355_normalize_u8(msk, n, s, s, 1, None, None, None, y)
         return x, y

@@ -74,21 +74,25 @@ def get_class_model(name, hub=None):
     return model, add_dropout_to_fc(model, p=0.5)
 
 
-def get_seg_model(name):
-    """name -> segmentation model instance (helpers.py:195-213)."""
+def get_seg_model(name, classes=1):
+    """name -> segmentation model instance (helpers.py:195-213).  ``classes`` > 1: a K-channel logit head for the multi-class
+    path (mi355.nn.MultiClassSegLoss, utils/multiclass.py); 1 = the reference's single-foreground model, built as before."""
     key = name.lower()
+    classes = int(classes)
+    if classes < 1:
+        raise ValueError(f"classes must be >= 1 (got {classes})")
     if key == "attentionunet":
         from models.segmentation_models.AttentionUNet import AttentionUNet
-        return AttentionUNet()
+        return AttentionUNet() if classes == 1 else AttentionUNet(out_channel=classes)
     if key == "r2unet":
         from models.segmentation_models.R2U_Net import R2U_Net
-        return R2U_Net()
+        return R2U_Net() if classes == 1 else R2U_Net(out_channels=classes)
     if key == "r2attunet":
         from models.segmentation_models.R2AttU_Net import R2AttU_Net
-        return R2AttU_Net()
+        return R2AttU_Net() if classes == 1 else R2AttU_Net(out_channels=classes)
     if key == "resnetunet":
         from models.segmentation_models.ResnetUnet import ResNetUnet
-        return ResNetUnet()
+        return ResNetUnet() if classes == 1 else ResNetUnet(n_classes=classes)
     raise ValueError(f"Unknown segmentation model: {name}")
 
 
@@ -231,7 +235,9 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
                 if seg and out.dim() == 3:
                     out = out.unsqueeze(1)
                 vloss += criterion(out, y) * x.size(0)
-                if seg:
+                if seg and hasattr(criterion, "val_metric"):
+                    vmetric += criterion.val_metric(out, y)      # multi-class criteria: mean IoU from the confusion matrix
+                elif seg:
                     vmetric += _iou_device(out.float(), y.float(), 0.5, is_logit=True)
                 else:
                     vmetric += (torch.argmax(out, 1) == y).sum()

@@ -550,9 +550,68 @@ _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "Attenti
               "R2Unet": "R2Unet_best_loss.pt", "R2AttUnet": "R2AttUnet_best_loss.pt", "CLIPSeg": "CLIPSeg_best_loss.pt"}
 
 
+def check_multiclass_options(seg_classes, surface=False, tta=None, sliding=None, auc=False, ci=None, calibration=None):
+    """seg_classes > 1 (tester.py --seg-classes) next to an option that is defined for one foreground: ValueError naming it."""
+    seg_classes = int(seg_classes)
+    if not 1 <= seg_classes <= 16:
+        raise ValueError(f"seg_classes must lie in [1, 16], got {seg_classes}")
+    if seg_classes == 1:
+        return seg_classes
+    bad = [name for name, on in (("--surface", surface), ("--tta", tta is not None), ("--sw-tile", sliding is not None), ("--auc", auc),
+                                 ("--ci", ci is not None and ci != 0), ("--calibration", calibration is not None)) if on]
+    if bad:
+        raise ValueError(f"--seg-classes {seg_classes}: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} defined for binary "
+                         "segmentation only (one foreground) and not supported with more than one class")
+    return seg_classes
+
+
+def evaluate_multiclass_segmentation_model(model, test_loader, device, model_name, num_classes, ignore_index=255, class_names=None):
+    """The segmentation eval loop for a K-channel model and class-index masks (uint8 [N, H, W]; ``ignore_index`` and every other
+    label >= K are left out): one argmax / confusion launch per batch (utils/multiclass.py), one read-back after the loop.  Returns
+    percentages like the binary loop: ``dice`` / ``iou`` (the means over the classes of the per-class means over the images — a
+    class in neither mask of an image is NaN there and counted out), ``pixel_accuracy``, ``dice_per_class`` / ``iou_per_class``
+    (lists in class order), and ``num_classes``, ``class_names``, ``samples``, ``confusion_matrix`` ([K][K] integers, label x
+    prediction, summed over the images)."""
+    from utils.multiclass import check_class_names, confusion_batch, metrics_from_confusion
+    num_classes = int(num_classes)
+    names = check_class_names(class_names, num_classes)
+    model.eval()
+    print(f"\n{'=' * 60}\nTesting Segmentation Model: {model_name} ({num_classes} classes)\n{'=' * 60}")
+    pending = []
+    with torch.no_grad():
+        for images, masks in test_loader:
+            out = model(images.to(device))
+            if out.dim() < 4 or out.shape[1] != num_classes:
+                raise ValueError(f"{model_name}: logits [N, {num_classes}, H, W] expected, got {tuple(out.shape)}")
+            pending.append(confusion_batch(out, masks.to(device), ignore_index))
+    if not pending:
+        raise ValueError("the test loader is empty")
+    conf = torch.cat(pending).cpu().numpy()           # single read-back after the loop
+    result = multiclass_result(metrics_from_confusion(conf), names, conf.shape[0])
+    for line in _multiclass_lines(result):
+        print(line)
+    return result
+
+
+def multiclass_result(m, class_names, samples):
+    """metrics_from_confusion's fractions -> the result dictionary of evaluate_multiclass_segmentation_model (percentages)."""
+    return {"iou": 100.0 * m["mean_iou"], "dice": 100.0 * m["mean_dice"], "pixel_accuracy": 100.0 * m["pixel_accuracy"],
+            "num_classes": len(class_names), "class_names": list(class_names), "samples": int(samples),
+            "dice_per_class": [100.0 * float(v) for v in m["dice_per_class"]],
+            "iou_per_class": [100.0 * float(v) for v in m["iou_per_class"]],
+            "confusion_matrix": np.asarray(m["confusion_matrix"]).tolist()}
+
+
+def _multiclass_lines(r):
+    lines = [f"Mean IoU:       {r['iou']:.2f}%", f"Mean Dice:      {r['dice']:.2f}%", f"Pixel Accuracy: {r['pixel_accuracy']:.2f}%",
+             f"{'Class':<20} {'IoU':<10} {'Dice':<10}"]
+    lines += [f"{n:<20} {i:>8.2f}% {d:>8.2f}%" for n, i, d in zip(r["class_names"], r["iou_per_class"], r["dice_per_class"])]
+    return lines
+
+
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
                     seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, ci=None, calibration=None,
-                    auc=False, calibration_bins=15, surface=False):
+                    seg_classes=1, seg_ignore_index=255, class_names=None, auc=False, calibration_bins=15, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -576,8 +635,12 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     written by trainer.py --calibrate) from that directory or its ``classification_models`` / ``segmentation_models`` sub-directory:
     the classifiers' temperature (with ``auc``: their ECE, Brier score and NLL are the calibrated ones; not together with ``tta``),
     the segmenters' threshold in place of 0.5 (also in the TTA and sliding-window folds).  A checkpoint without a sidecar:
-    FileNotFoundError naming the file."""
+    FileNotFoundError naming the file.
+    ``seg_classes`` K > 1 (with ``seg_ignore_index``, ``class_names``): the segmenters are built with K-channel heads, the default
+    segmentation loader yields class-index masks (SegmentationDataset(labels=True)) and every segmenter goes through
+    evaluate_multiclass_segmentation_model; the binary-only options (check_multiclass_options) raise ValueError."""
     from utils.helpers import get_class_model, get_seg_model
+    seg_classes = check_multiclass_options(seg_classes, surface, tta, sliding, auc, ci, calibration)
     ci = _check_ci(ci)
     size = IMG_SIZE if size is None else int(size)
     if size < 1:
@@ -636,7 +699,11 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             from utils.dataset import ClassificationDataset, GpuBatchLoader, SegmentationDataset
             from utils.gpu_transforms import ClsBatchTransform, SegBatchTransform
             if seg:
-                ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(size, train=False, device=device, clahe=clahe), split="test")
+                if seg_classes > 1:
+                    ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(size, train=False, device=device, clahe=clahe, labels=True),
+                                             split="test", labels=True)
+                else:
+                    ds = SegmentationDataset(DATA_ROOT, SegBatchTransform(size, train=False, device=device, clahe=clahe), split="test")
                 return GpuBatchLoader(ds, max(1, batch_size // 2), shuffle=False, device=device)
             ds = ClassificationDataset(DATA_ROOT, ClsBatchTransform(IMG_SIZE, train=False, device=device, clahe=clahe), split="test")
             return GpuBatchLoader(ds, batch_size, shuffle=False, device=device)
@@ -693,7 +760,11 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
                 elif tta is not None:
                     m = TTASegmenter(m, tta, tta_merge, t)
                 return evaluate_segmentation_model_ci(m, l, d, name, surface=surface, auc=auc, ci=ci, calibration=cals[name])
-        run(_SEG_FILES, seg_weights_dir, seg_loader, get_seg_model, seg_test, "Segmentation")
+        seg_build = get_seg_model
+        if seg_classes > 1:
+            seg_build = lambda n: get_seg_model(n, classes=seg_classes)  # noqa: E731
+            seg_test = lambda m, l, d, name: evaluate_multiclass_segmentation_model(m, l, d, name, seg_classes, seg_ignore_index, class_names)  # noqa: E731
+        run(_SEG_FILES, seg_weights_dir, seg_loader, seg_build, seg_test, "Segmentation")
     return results
 
 
@@ -725,7 +796,11 @@ def print_summary(results):
             for model in rank_models:
                 m = results[model]
                 print(f"{model:<20} {m['auroc']:>8.4f}   {m['average_precision']:>8.4f}   {m['ece']:>8.4f}   {m['brier']:>8.4f}   {m['nll']:>8.4f}")
-    seg_models = [m for m in ["ResNetUnet", "AttentionUNet", "R2Unet", "R2AttUnet", "CLIPSeg"] if m in results]
+    seg_all = [m for m in ["ResNetUnet", "AttentionUNet", "R2Unet", "R2AttUnet", "CLIPSeg"] if m in results]
+    mc_models = [m for m in seg_all if "num_classes" in results[m]]      # (only after test_all_models(seg_classes=K > 1))
+    seg_models = [m for m in seg_all if m not in mc_models]
+    for line in multiclass_summary_lines(results, mc_models):
+        print(line)
     if seg_models:
         print("\n\nSEGMENTATION MODELS:")
         print("-" * 80)
@@ -756,6 +831,24 @@ def print_summary(results):
                 m = results[model]
                 print(f"{model:<20} {m['pixel_auroc']:>11.4f}   {m['pixel_ap']:>9.4f}   {m.get('auc_samples', ''):>7}")
     print("=" * 80 + "\n")
+
+
+def multiclass_summary_lines(results, models):
+    """The multi-class table of print_summary: one row of means per model, then each model's per-class IoU / Dice."""
+    if not models:
+        return []
+    lines = ["\n\nSEGMENTATION MODELS, MULTI-CLASS (means over the classes):", "-" * 80,
+             f"{'Model':<20} {'Classes':<8} {'mIoU':<10} {'mDice':<10} {'Pixel Acc':<12} {'Samples':<8}", "-" * 80]
+    for model in models:
+        m = results[model]
+        lines.append(f"{model:<20} {m['num_classes']:>7} {m['iou']:>8.2f}% {m['dice']:>8.2f}% {m['pixel_accuracy']:>10.2f}% {m.get('samples', ''):>7}")
+    best = max(models, key=lambda x: results[x]["dice"])
+    lines.append(f"\n\U0001F3C6 Best Segmentation Model: {best} (Mean Dice: {results[best]['dice']:.2f}%)")
+    for model in models:
+        m = results[model]
+        lines += [f"\n{model}, per class (IoU / Dice):"]
+        lines += [f"  {n:<18} {i:>8.2f}% {d:>8.2f}%" for n, i, d in zip(m["class_names"], m["iou_per_class"], m["dice_per_class"])]
+    return lines
 
 
 def print_paired_tests(results, ci):
@@ -811,14 +904,18 @@ def print_paired_tests(results, ci):
 
 
 def _csv_row(name, result):
-    """scalars only; a ``<key>_ci`` pair becomes the columns ``<key>_lo`` and ``<key>_hi``"""
+    """scalars only; a ``<key>_ci`` pair becomes the columns ``<key>_lo`` and ``<key>_hi``, a multi-class result's per-class lists
+    the columns ``dice_<class name>`` / ``iou_<class name>``"""
     row = {"Model": name}
     for k, v in result.items():
         if k.endswith("_ci") and isinstance(v, tuple):
             row[k[:-3] + "_lo"], row[k[:-3] + "_hi"] = v
+        elif k in ("dice_per_class", "iou_per_class") and "class_names" in result:      # multi-class: one column per class
+            for n, x in zip(result["class_names"], v):
+                row[f"{k[:-10]}_{n}"] = x
         else:
             row[k] = v
-    for k in ("confusion_matrix", "precision_per_class", "recall_per_class", "f1_per_class", "auroc_per_class", "ap_per_class",
+    for k in ("confusion_matrix", "class_names", "precision_per_class", "recall_per_class", "f1_per_class", "auroc_per_class", "ap_per_class",
               "ci_detail", "auroc_ci_per_class", "auroc_se_per_class", "auroc_delong_ci_per_class"):
         row.pop(k, None)
     return row
@@ -873,12 +970,28 @@ def build_parser():
                      help="bootstrap replicates (up to 8192) for a percentile interval on every figure and paired tests between the models; 0 = off")
     _ap.add_argument("--ci-level", type=float, default=0.95, help="--ci: the level of the intervals")
     _ap.add_argument("--ci-seed", type=int, default=0, help="--ci: the seed of the resamples (shared by every model)")
+    _ap.add_argument("--seg-classes", type=int, default=1,
+                     help="K > 1: the segmentation checkpoints have K-channel heads and the masks hold class indices (grey value = class, "
+                          "255 = ignore): per-class and mean Dice / IoU, pixel accuracy and the confusion matrix (utils/multiclass.py)")
+    _ap.add_argument("--seg-ignore-index", type=int, default=255, help="--seg-classes: the label left out of every count (-1: none)")
+    _ap.add_argument("--class-names", default=None, help="--seg-classes: comma-separated names of the K classes, in class order")
     return _ap
+
+
+def multiclass_kwargs(args):
+    """tester.py --seg-classes K [--seg-ignore-index] [--class-names]: the keyword arguments of test_all_models ({} for K = 1),
+    after the clear error for an option that is binary-only."""
+    k = check_multiclass_options(args.seg_classes, args.surface, args.tta, (args.sw_tile or None) and (args.sw_tile,), args.auc,
+                                 args.ci, args.calibration)
+    if k == 1:
+        return {}
+    from utils.multiclass import check_class_names
+    return {"seg_classes": k, "seg_ignore_index": args.seg_ignore_index, "class_names": check_class_names(args.class_names, k)}
 
 
 if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898): same banner, same three calls
     _args = build_parser().parse_args()
-    _kw = {}
+    _kw = multiclass_kwargs(_args)
     if _args.clahe_clip != 0:
         from utils.clahe import check_clahe
         _kw["clahe"] = check_clahe(_args.clahe_clip, _args.clahe_grid)

@@ -14,6 +14,7 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task seg --model attentionunet --data-root dataset --clahe-clip 4 --clahe-grid 8
     python utils/trainer.py --task cls --model resnet18 --mixup-alpha 0.2 --cutmix-alpha 1.0 --class-weight balanced
     python utils/trainer.py --task seg --model attentionunet --cutmix-alpha 1.0 --mix-prob 0.5
+    python utils/trainer.py --task seg --model attentionunet --seg-classes 3 --seg-ce-weight 0.5 --seg-dice-weight 0.5
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -44,7 +45,11 @@ CLS_MODELS = ["resnet18", "resnet50", "vgg16", "vgg19"]
 SEG_MODELS = ["resnetunet", "attentionunet", "r2unet", "r2attunet"]
 
 
-def synthetic_dataset(task, n, size, seed=0):
+def synthetic_dataset(task, n, size, seed=0, classes=1):
+    """``classes`` K > 1 (seg): nested, offset ellipses inside the K = 1 ellipse give uint8 labels 0 .. K - 1 [n, size, size], each
+    class tinted differently; K = 1 is the binary set, tensor for tensor."""
+    if classes != 1 and (task != "seg" or not 2 <= classes <= 16):
+        raise ValueError(f"classes > 1 is for task 'seg' with 2 <= classes <= 16 (task={task!r}, classes={classes})")
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(n, 3, size, size, generator=g)
     if task == "cls":
@@ -53,6 +58,16 @@ def synthetic_dataset(task, n, size, seed=0):
     c = torch.rand(n, 4, generator=g)
     cy, cx = (0.4 + 0.2 * c[:, 0]) * size, (0.4 + 0.2 * c[:, 1]) * size
     ry, rx = (0.25 + 0.1 * c[:, 2]) * size, (0.25 + 0.1 * c[:, 3]) * size
+    if classes > 1:
+        lab = torch.zeros(n, size, size, dtype=torch.uint8)
+        for k in range(1, classes):          # ellipse k: the outer one shrunk by (K - k) / (K - 1), its centre pushed towards +x / +y
+            f = (classes - k) / (classes - 1)
+            oy, ox = cy + 0.15 * (1 - f) * ry, cx + 0.25 * (1 - f) * rx
+            inside = (((yy[None] - oy[:, None, None]) / (f * ry[:, None, None])) ** 2 +
+                      ((xx[None] - ox[:, None, None]) / (f * rx[:, None, None])) ** 2) <= 1
+            lab[inside] = k
+        tint = torch.tensor([[0.0, 0.0, 0.0]] + [[1.0 - 0.35 * k, -0.7 + 0.45 * k, 0.4 * (-1) ** k + 0.1 * k] for k in range(classes - 1)])
+        return TensorDataset(x + tint[lab.long()].permute(0, 3, 1, 2), lab)
     m = ((((yy[None] - cy[:, None, None]) / ry[:, None, None]) ** 2 + ((xx[None] - cx[:, None, None]) / rx[:, None, None]) ** 2) <= 1).float()
     return TensorDataset(x + m[:, None] * torch.tensor([1.0, -0.7, 0.4]).view(1, 3, 1, 1), m[:, None])
 
@@ -105,6 +120,13 @@ def build_parser():
     ap.add_argument("--mix-per-sample", action="store_true", help="mixup / CutMix: a draw per sample (default: one per batch)")
     ap.add_argument("--class-weight", choices=["none", "balanced"], default="none",
                     help="cls: per-class loss weights n / (C * count_c) from the training files (--data-root; ignored for synthetic data)")
+    ap.add_argument("--seg-classes", type=int, default=1,
+                    help="seg: K > 1 trains K-channel heads on class-index masks (grey value = class, 255 = ignore) under softmax "
+                         "cross-entropy + per-class Dice (mi355.nn.MultiClassSegLoss); 1 = the binary path")
+    ap.add_argument("--seg-ce-weight", type=float, default=1.0, help="--seg-classes: weight of the cross-entropy term")
+    ap.add_argument("--seg-dice-weight", type=float, default=0.0, help="--seg-classes: weight of the per-class Dice term")
+    ap.add_argument("--seg-ignore-index", type=int, default=255, help="--seg-classes: the label left out of loss and metrics (-1: none)")
+    ap.add_argument("--seg-class-weight", default=None, help="--seg-classes: comma-separated cross-entropy weights w0,w1,... one per class")
     ap.add_argument("--calibrate", action="store_true",
                     help="after training, fit the post-hoc calibration of the best checkpoint on the validation split (utils/calibrate.py): "
                          "a classifier's temperature, a segmenter's Dice-optimal mask threshold; written next to the checkpoint as "
@@ -196,10 +218,47 @@ def cls_criterion(args, batch_mix, dataset=None, indices=None, say=print):
     return mnn.MixCrossEntropyLoss(label_smoothing=0.1, weight=w)
 
 
+def multiclass_arg(args):
+    """--seg-classes K: 1 -> None (the binary path, untouched); K > 1 -> the keyword arguments of mi355.nn.MultiClassSegLoss, after a
+    clear error for every flag that is defined for one foreground only — raised here, before any data is read."""
+    k = int(args.seg_classes)
+    if k == 1:
+        return None
+    if not 2 <= k <= 16:
+        raise ValueError(f"--seg-classes must lie in [1, 16] ({k})")
+    if args.task != "seg":
+        raise ValueError(f"--seg-classes {k} is for --task seg (got --task {args.task})")
+    bad = [flag for flag, on in (("--seg-loss lovasz", args.seg_loss == "lovasz"), ("--boundary-weight", args.boundary_weight != 0),
+                                 ("--lovasz-weight", args.lovasz_weight != 0), ("--cutmix-alpha", args.cutmix_alpha != 0),
+                                 ("--mixup-alpha", args.mixup_alpha != 0), ("--calibrate", args.calibrate)) if on]
+    if bad:
+        raise ValueError(f"--seg-classes {k}: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} defined for binary segmentation "
+                         "only (one foreground) and cannot be combined with more than one class")
+    w = None
+    if args.seg_class_weight is not None:
+        try:
+            w = [float(v) for v in args.seg_class_weight.split(",")]
+        except ValueError:
+            raise ValueError(f"--seg-class-weight must be comma-separated numbers ({args.seg_class_weight!r})") from None
+        if len(w) != k or any(not (v >= 0 and v != float("inf")) for v in w):
+            raise ValueError(f"--seg-class-weight must hold {k} finite weights >= 0 ({args.seg_class_weight!r})")
+    if args.seg_ce_weight < 0 or args.seg_dice_weight < 0:
+        raise ValueError(f"--seg-ce-weight and --seg-dice-weight must not be negative ({args.seg_ce_weight}, {args.seg_dice_weight})")
+    if args.seg_ignore_index != -1 and not k <= args.seg_ignore_index <= 255:
+        raise ValueError(f"--seg-ignore-index must be -1 or lie in [{k}, 255] ({args.seg_ignore_index})")
+    return dict(num_classes=k, ce_weight=args.seg_ce_weight, dice_weight=args.seg_dice_weight, class_weight=w,
+                ignore_index=args.seg_ignore_index, per_sample=args.dice_per_sample)
+
+
 def seg_criterion(args):
     """The loss module --seg-loss asks for; None = train()'s own default (BCEWithLogits).  With --boundary-weight > 0 it is that
     regional loss plus the boundary loss, as one criterion (mi355.nn.RegionBoundaryLoss); with --lovasz-weight > 0 that regional loss
-    plus the Lovasz hinge (mi355.nn.RegionLovaszLoss).  Three terms are not combined."""
+    plus the Lovasz hinge (mi355.nn.RegionLovaszLoss).  Three terms are not combined.  With --seg-classes K > 1:
+    mi355.nn.MultiClassSegLoss (multiclass_arg)."""
+    mc = multiclass_arg(args)
+    if mc is not None:
+        from mi355 import nn as mnn
+        return mnn.MultiClassSegLoss(**mc)
     if args.boundary_weight < 0:
         raise ValueError(f"--boundary-weight must not be negative ({args.boundary_weight})")
     if args.lovasz_weight < 0:
@@ -257,6 +316,8 @@ def main():
     results = {}
     tasks = ["cls", "seg"] if args.task == "both" else [args.task]
     mixes = {task: mix_arg(args, task, rank) for task in tasks}          # (a bad flag fails before any data is read)
+    multi = multiclass_arg(args) is not None
+    seg_labels = {"labels": True} if multi else {}
     for task in tasks:
         names = [args.model] if args.model else (CLS_MODELS if task == "cls" else SEG_MODELS)
         bs = 16 if task == "cls" else 8
@@ -264,8 +325,9 @@ def main():
             from utils.dataset import ClassificationDataset, GpuBatchLoader, SegmentationDataset
             from utils.gpu_transforms import ClsBatchTransform, SegBatchTransform
             DS, TF = (ClassificationDataset, ClsBatchTransform) if task == "cls" else (SegmentationDataset, SegBatchTransform)
-            ds_tr = DS(args.data_root, TF(args.size, train=True, device=device, elastic=elastic_arg(args), clahe=clahe_arg(args)), "train")
-            ds_va = DS(args.data_root, TF(args.size, train=False, device=device, clahe=clahe_arg(args)), "train")
+            kw = seg_labels if task == "seg" else {}
+            ds_tr = DS(args.data_root, TF(args.size, train=True, device=device, elastic=elastic_arg(args), clahe=clahe_arg(args), **kw), "train", **kw)
+            ds_va = DS(args.data_root, TF(args.size, train=False, device=device, clahe=clahe_arg(args), **kw), "train", **kw)
             if len(ds_tr) == 0:
                 say(f"{task} dataset is empty under {args.data_root}. Skipping.")
                 continue
@@ -274,7 +336,7 @@ def main():
             train_dl = GpuBatchLoader(ds_tr, bs, shuffle=True, device=device, indices=perm[:n_train])
             val_dl = GpuBatchLoader(ds_va, bs, shuffle=True, device=device, indices=perm[n_train:])
         else:
-            full = synthetic_dataset(task, args.samples, args.size)
+            full = synthetic_dataset(task, args.samples, args.size, classes=args.seg_classes if task == "seg" else 1)
             n_train = int(0.8 * len(full))
             tr, va = random_split(full, [n_train, len(full) - n_train], generator=split_gen) if split_gen is not None else \
                 random_split(full, [n_train, len(full) - n_train])
@@ -294,7 +356,7 @@ def main():
                 if args.calibrate:
                     calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "classification_models"), False, say)
             else:
-                model = get_seg_model(name)
+                model = get_seg_model(name, classes=args.seg_classes)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True,
                              criterion=seg_criterion(args))
                 if args.calibrate:
