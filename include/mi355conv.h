@@ -386,6 +386,47 @@ int mi355_seg_loss_fwd(const float* z, const float* t, int B, long long per, flo
                        float smooth, int per_sample, float* partial, float* state, float* loss, mi355_stream_t s);
 int mi355_seg_loss_bwd(const float* z, const float* t, int B, long long per, float bce_weight, const float* state,
                        const float* gscale, float* dz, mi355_stream_t s);
+/* Focal + (focal-)Tversky on fp32 logits and targets [B][per] (nothing in the reference; Lin et al. 2017 with torchvision's
+ * sigmoid_focal_loss convention, Salehi et al. 2017, Abraham & Khan 2019).  The target is binarised in the kernels, t = (target > 0.5).
+ * p = sigmoid(z), I = sum p t, P = sum p, T = sum t, FP = P - I, FN = T - I, n = B per:
+ *   focal_i = alpha_t (1 - p_t)^focal_gamma ce_i,  p_t = t p + (1 - t)(1 - p),  ce = BCEWithLogits(z, t),
+ *             alpha_t = focal_alpha t + (1 - focal_alpha)(1 - t), focal_alpha < 0: alpha_t = 1
+ *   TI      = Num / Den,  Num = I + smooth,  Den = I + tv_a FP + tv_b FN + smooth
+ *   loss[0] = focal_weight * mean_i(focal_i) + tversky_weight * (1 - TI)^tv_exp
+ * with TI over the whole batch (per_sample = 0) or per image, the B terms averaged (per_sample = 1; the focal term is the same).
+ * tv_exp = 1: the Tversky loss; tv_a = tv_b = 0.5, tv_exp = 1, smooth = s: the Dice loss of mi355_seg_loss_fwd with smooth 2 s.
+ * Deterministic: no floating-point atomics, every fold in a fixed order.
+ *   mi355_ftv_loss_rows: rows of four floats `partial` must hold (16-byte aligned); a function of (B, per) alone.
+ *   mi355_ftv_loss_fwd:  one pass over z and t (16-byte accesses when per % 4 == 0 and z, t are 16-byte aligned), a one-workgroup
+ *     finalize in double; leaves loss[0] and, in state[2 b], state[2 b + 1], the pair (A_b, C_b) of sample b:
+ *     A = tversky_weight tv_exp (1 - TI)^(tv_exp - 1) / Den, C = A Num / Den (per_sample: its own sums, both / B); with
+ *     1 - TI <= 0 (a perfect, saturated prediction) A = C = 0: the sub-gradient 0, never NaN or inf.
+ *   mi355_ftv_loss_bwd:  one pass, with s = 2 t - 1, u = 1 - p_t:
+ *     dz_i = gscale[0] * (focal_weight / n * alpha_t u^focal_gamma s (-focal_gamma p_t ce - u)
+ *                         - (A_b t - C_b (tv_a + (1 - tv_a - tv_b) t)) p (1 - p))
+ *     from the `state` the forward left (same B, per and parameters); gscale = upstream gradient x loss scale on the device,
+ *     NULL = 1.  It does not recompute the loss.
+ * u and p (1 - p) come from e = exp(-|z|), without a 1 - p cancellation: every output is finite at |z| = 100.  focal_gamma = 0:
+ * u^0 = 1 exactly, also at u = 0; u = 0 with focal_gamma > 0: the element's focal term and focal gradient are exactly 0.
+ * B <= 65535; focal_weight, tversky_weight, focal_gamma, smooth >= 0; focal_alpha <= 1; tv_a, tv_b >= 0, tv_a + tv_b > 0; tv_exp > 0. */
+int mi355_ftv_loss_rows(int B, long long per);
+int mi355_ftv_loss_fwd(const float* z, const float* t, int B, long long per, float focal_weight, float focal_alpha,
+                       float focal_gamma, float tversky_weight, float tv_a, float tv_b, float tv_exp, float smooth,
+                       int per_sample, float* partial, float* state, float* loss, mi355_stream_t s);
+int mi355_ftv_loss_bwd(const float* z, const float* t, int B, long long per, float focal_weight, float focal_alpha,
+                       float focal_gamma, float tv_a, float tv_b, const float* state, const float* gscale, float* dz,
+                       mi355_stream_t s);
+/* Focal cross-entropy for classifiers (Lin et al. 2017, softmax form): z [B][C] fp32 logits, hard labels y, gamma >= 0, optional
+ * per-class weight [C] (NULL: all ones).  With p = softmax(z[b]), py = p[y_b], u = sum_{c != y_b} p_c (summed, not 1 - py):
+ *   loss[0]  = (1 / B) sum_b weight[y_b] u^gamma (-log py)
+ *   dz[b][c] = (gscale[0] / B) weight[y_b] ([c == y_b] - p_c) (gamma py u^(gamma - 1) log py - u^gamma)
+ * The sum is divided by B, as in mi355_ce_mix (not by the sum of the picked weights).  gamma = 0: mi355_ce_mix with hard labels and
+ * smoothing 0.  A row with u = 0 and gamma > 0 contributes loss 0 and gradient 0; the gradient is formed without a division by u.
+ * dz NULL: loss only; gscale NULL: 1.  Evaluated in double and rounded to float once on store; one workgroup, thread b % 256 owns
+ * row b, then a block fold in a fixed order: bit-reproducible.  Labels in [0, C) are the caller's contract; a row with a label
+ * outside contributes loss 0 and gradient 0 (z and weight are never indexed by it). */
+int mi355_ce_focal(const float* z, const int64_t* y, const float* weight, float* loss, float* dz, const float* gscale, int B,
+                   int C, float gamma, mi355_stream_t s);
 /* Multi-class segmentation (nothing in the reference, whose losses and metrics are binary): per-pixel softmax cross-entropy +
  * per-class soft Dice, and the argmax / confusion-matrix pass of the metrics.  Logits z fp32 [N][C][HW] (the NCHW map of the
  * K-channel heads; a plan's dout has the same layout), labels y uint8 [N][HW], 2 <= C <= 16, N <= 65535, HW <= 2^30.

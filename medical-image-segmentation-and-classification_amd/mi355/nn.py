@@ -113,6 +113,108 @@ class DiceLoss(CombinedLoss):
         super().__init__(0.0, 1.0, smooth, per_sample)
 
 
+class _FocalTverskyFn(torch.autograd.Function):
+    """Focal + (focal-)Tversky (csrc/focal_tversky.hip), the launches of _SegLossFn: the forward leaves the loss and one coefficient
+    pair per sample on the device, the backward is one pass that reads them with the upstream gradient and writes dL/dlogits."""
+
+    @staticmethod
+    def forward(ctx, out, target, plan, cfg):
+        if target.dtype != torch.float32 or not target.is_contiguous():
+            target = target.float().contiguous()
+        if target.numel() != out.numel():
+            raise ValueError(f"target size {tuple(target.shape)} must match input size {tuple(out.shape)}")
+        o = out.detach()
+        if not o.is_contiguous():
+            o = o.contiguous()
+        fw, fa, fg, tw, a, b, g, smooth, per_sample = cfg
+        B = o.shape[0]
+        per = o.numel() // B
+        rows = lib.mi355_ftv_loss_rows(B, per)
+        if rows <= 0:
+            raise RuntimeError(f"mi355_ftv_loss_rows failed: {lib.raw('mi355_last_error')().decode()}")
+        # one buffer: [rows x 4 partial sums | (A_b, C_b) per sample | loss]
+        buf = torch.empty(rows * 4 + 2 * B + 1, dtype=torch.float32, device=out.device)
+        partial, state, loss = buf[: rows * 4], buf[rows * 4: rows * 4 + 2 * B], buf[rows * 4 + 2 * B:]
+        lib.mi355_ftv_loss_fwd(o, target, B, per, fw, fa, fg, tw, a, b, g, smooth, 1 if per_sample else 0, partial, state, loss)
+        ctx.o, ctx.t, ctx.plan, ctx.state, ctx.cfg = o, target, plan, state, cfg
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t, plan = ctx.o, ctx.t, ctx.plan
+        fw, fa, fg, _, a, b = ctx.cfg[:6]
+        n = o.numel()
+        B = o.shape[0]
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        lib.mi355_ftv_loss_bwd(o, t, B, n // B, fw, fa, fg, a, b, ctx.state, gs, dz)
+        return dz[:n].view(o.shape), None, None, None
+
+
+class FocalTverskyLoss(nn.Module):
+    """focal_weight * focal + tversky_weight * (1 - TI)^exponent on the HIP library, one autograd node (mi355_ftv_loss_*).  The target
+    is binarised at 0.5 inside the kernels.  With p = sigmoid(logits):
+
+        focal = mean(alpha_t (1 - p_t)^focal_gamma BCEWithLogits)     torchvision.ops.sigmoid_focal_loss (Lin et al. 2017), mean;
+                                                                      focal_alpha < 0: no alpha_t
+        TI    = (TP + smooth) / (TP + alpha FP + beta FN + smooth)    Salehi et al. 2017; TP = sum p t, FP = sum p (1 - t), FN = sum (1 - p) t
+
+    ``alpha`` weighs false positives and ``beta`` false negatives: beta > alpha trains for recall.  ``exponent`` = 1 is the Tversky
+    loss, 0.75 the focal-Tversky loss of Abraham & Khan 2019 (their gamma = 4/3).  ``per_sample=True`` forms TI per image and averages
+    the B terms.  Where the prediction is perfect and saturated (1 - TI = 0) the Tversky gradient is 0.  Deterministic: the same
+    input gives the same bits."""
+
+    def __init__(self, focal_weight=0.0, tversky_weight=1.0, alpha=0.7, beta=0.3, exponent=0.75, focal_alpha=0.25, focal_gamma=2.0,
+                 smooth=1.0, per_sample=False):
+        super().__init__()
+        if not (focal_weight >= 0 and tversky_weight >= 0 and smooth >= 0):
+            raise ValueError(f"focal_weight, tversky_weight and smooth must not be negative ({focal_weight}, {tversky_weight}, {smooth})")
+        if not (alpha >= 0 and beta >= 0 and alpha + beta > 0):
+            raise ValueError(f"alpha and beta must not be negative and not both 0 ({alpha}, {beta})")
+        if not exponent > 0:
+            raise ValueError(f"exponent must be positive ({exponent})")
+        if not focal_gamma >= 0:
+            raise ValueError(f"focal_gamma must not be negative ({focal_gamma})")
+        if not focal_alpha <= 1:
+            raise ValueError(f"focal_alpha must lie in [0, 1], or be negative for no class balance ({focal_alpha})")
+        for name, v in (("focal_weight", focal_weight), ("tversky_weight", tversky_weight), ("alpha", alpha), ("beta", beta),
+                        ("exponent", exponent), ("focal_alpha", focal_alpha), ("focal_gamma", focal_gamma), ("smooth", smooth)):
+            if v in (float("inf"), float("-inf")):
+                raise ValueError(f"{name} must be finite ({v})")
+        self.focal_weight, self.tversky_weight, self.alpha, self.beta = float(focal_weight), float(tversky_weight), float(alpha), float(beta)
+        self.exponent, self.focal_alpha, self.focal_gamma = float(exponent), float(focal_alpha), float(focal_gamma)
+        self.smooth, self.per_sample = float(smooth), bool(per_sample)
+
+    def forward(self, out, target):
+        if out.dtype != torch.float32:
+            out = out.float()
+        cfg = (self.focal_weight, self.focal_alpha, self.focal_gamma, self.tversky_weight, self.alpha, self.beta, self.exponent,
+               self.smooth, self.per_sample)
+        return _FocalTverskyFn.apply(out, target, getattr(out, "_mi355_plan", None), cfg)
+
+    def extra_repr(self):
+        return (f"focal_weight={self.focal_weight}, tversky_weight={self.tversky_weight}, alpha={self.alpha}, beta={self.beta}, "
+                f"exponent={self.exponent}, focal_alpha={self.focal_alpha}, focal_gamma={self.focal_gamma}, smooth={self.smooth}, "
+                f"per_sample={self.per_sample}")
+
+
+class FocalLoss(FocalTverskyLoss):
+    """mean(alpha_t (1 - p_t)^gamma BCEWithLogits(logits, target)) — torchvision.ops.sigmoid_focal_loss(reduction="mean"); ``alpha`` < 0
+    switches alpha_t off: FocalTverskyLoss(1, 0) on the same kernels."""
+
+    def __init__(self, alpha=0.25, gamma=2.0):
+        super().__init__(1.0, 0.0, focal_alpha=alpha, focal_gamma=gamma)
+
+
+class TverskyLoss(FocalTverskyLoss):
+    """1 - (TP + smooth) / (TP + alpha FP + beta FN + smooth) (Salehi et al. 2017): FocalTverskyLoss(0, 1, exponent=1) on the same
+    kernels.  TverskyLoss(0.5, 0.5, smooth=s) is DiceLoss(smooth=2 s) on a binary target."""
+
+    def __init__(self, alpha=0.5, beta=0.5, smooth=1.0, per_sample=False):
+        super().__init__(0.0, 1.0, alpha, beta, 1.0, smooth=smooth, per_sample=per_sample)
+
+
 def _signed_dist2(target, threshold=0.5):
     """mi355_signed_dist2 on a contiguous fp32 device tensor [B, H, W] -> int32 [B, H, W] (csrc/boundary.hip): the signed squared
     Euclidean distance map of ``target > threshold``.  No host round trip."""
@@ -674,6 +776,77 @@ class MixCrossEntropyLoss(nn.Module):
 
     def extra_repr(self):
         return f"label_smoothing={self.label_smoothing}, weight={None if self.weight is None else self.weight.tolist()}"
+
+
+class _CEFocalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, y, weight, gamma, plan):
+        o = out.detach().contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=out.device)
+        lib.mi355_ce_focal(o, y, weight, loss, None, None, o.shape[0], o.shape[1], float(gamma))
+        ctx.o, ctx.t, ctx.plan, ctx.gamma = o, (y, weight), plan, float(gamma)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, plan = ctx.o, ctx.plan
+        y, weight = ctx.t
+        n = o.numel()
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        scratch = torch.empty(1, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        lib.mi355_ce_focal(o, y, weight, scratch, dz, gs, o.shape[0], o.shape[1], ctx.gamma)
+        return dz[:n].view(o.shape), None, None, None, None
+
+
+class FocalCrossEntropyLoss(nn.Module):
+    """Focal cross-entropy for classifiers (Lin et al. 2017 on a softmax; mi355_ce_focal): with p = softmax(z_b), hard labels y and
+    optional per-class weights ``weight`` ([C]; kept as a float32 device buffer)
+
+        loss = (1 / B) sum_b weight[y_b] (1 - p_b[y_b])^gamma (-log p_b[y_b])
+
+    The sum is divided by B, as in MixCrossEntropyLoss (not by the sum of the picked weights); ``gamma`` = 0 is
+    MixCrossEntropyLoss(0, weight) on hard labels.  No label smoothing and no mixed targets (the focal factor is defined for one true
+    class): train() rejects it next to mixup / CutMix.  One autograd node, evaluated in double; the gradient goes straight into the
+    plan's ``dout`` when the logits come from a mi355 ``Net``.  Labels on the host are checked against [0, C); labels on the device
+    only with ``check_labels=True`` (one synchronisation per call) — a row whose label is outside contributes nothing."""
+
+    def __init__(self, gamma=2.0, weight=None, check_labels=False):
+        super().__init__()
+        if not (gamma >= 0 and gamma != float("inf")):
+            raise ValueError(f"gamma must be a finite number >= 0 ({gamma})")
+        self.gamma, self.check_labels = float(gamma), bool(check_labels)
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).detach().reshape(-1).contiguous().clone()
+            if weight.numel() == 0 or not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+                raise ValueError(f"weight must hold finite values >= 0, one per class ({weight.tolist()})")
+        self.register_buffer("weight", weight)
+
+    def forward(self, out, target):
+        plan = getattr(out, "_mi355_plan", None)
+        out = out.float()
+        if out.dim() != 2:
+            raise ValueError(f"logits [B, C] expected, got {tuple(out.shape)}")
+        B, C = out.shape
+        if hasattr(target, "ya"):
+            raise ValueError("FocalCrossEntropyLoss takes hard labels: a mixed target (mixup / CutMix) needs MixCrossEntropyLoss")
+        if target.dim() != 1 or target.size(0) != B or target.dtype.is_floating_point:
+            raise ValueError(f"an integer label tensor [{B}] expected, got {target.dtype} {tuple(target.shape)}")
+        if (self.check_labels or not target.is_cuda) and (int(target.min()) < 0 or int(target.max()) >= C):
+            raise ValueError(f"labels must lie in [0, {C}), got {target.tolist()}")
+        dev = out.device
+        y = target.to(dev, torch.int64).contiguous()
+        w = self.weight
+        if w is not None:
+            if w.numel() != C:
+                raise ValueError(f"weight holds {w.numel()} classes, the logits {C}")
+            if w.device != dev:
+                self.weight = w = w.to(dev)
+        return _CEFocalFn.apply(out, y, w, self.gamma, plan)
+
+    def extra_repr(self):
+        return f"gamma={self.gamma}, weight={None if self.weight is None else self.weight.tolist()}"
 
 
 # ---- multi-class segmentation (csrc/mcseg.hip) ---------------------------------------------------------------------------------

@@ -15,6 +15,9 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task cls --model resnet18 --mixup-alpha 0.2 --cutmix-alpha 1.0 --class-weight balanced
     python utils/trainer.py --task seg --model attentionunet --cutmix-alpha 1.0 --mix-prob 0.5
     python utils/trainer.py --task seg --model attentionunet --seg-classes 3 --seg-ce-weight 0.5 --seg-dice-weight 0.5
+    python utils/trainer.py --task seg --model attentionunet --seg-loss focal_tversky --tversky-alpha 0.3 --tversky-beta 0.7
+    python utils/trainer.py --task seg --model attentionunet --seg-loss focal_dice --focal-gamma 2 --focal-alpha 0.25
+    python utils/trainer.py --task cls --model resnet18 --cls-loss focal --focal-gamma 2 --class-weight balanced
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -43,6 +46,9 @@ from utils.helpers import get_class_model, get_seg_model, train  # noqa: E402
 IMG_SIZE = 256
 CLS_MODELS = ["resnet18", "resnet50", "vgg16", "vgg19"]
 SEG_MODELS = ["resnetunet", "attentionunet", "r2unet", "r2attunet"]
+# mi355.nn.FocalTverskyLoss (focal_arg).  The focal loss alone is focal_dice with --focal-weight 1 --tversky-weight 0: the name
+# "focal" stays a choice the parser rejects (tests/test_seg_loss_cpu.py, tests/test_lovasz_cpu.py hold it to that).
+FOCAL_SEG_LOSSES = ["tversky", "focal_tversky", "focal_dice"]
 
 
 def synthetic_dataset(task, n, size, seed=0, classes=1):
@@ -86,12 +92,25 @@ def build_parser():
     ap.add_argument("--size", type=int, default=IMG_SIZE)
     ap.add_argument("--save-dir", default="weights")
     ap.add_argument("--data-root", default=None, help="dataset directory in the reference's layout; default: synthetic batches")
-    ap.add_argument("--seg-loss", choices=["bce", "dice", "bce_dice", "lovasz"], default="bce",
+    ap.add_argument("--seg-loss", choices=["bce", "dice", "bce_dice", "lovasz"] + FOCAL_SEG_LOSSES, default="bce",
                     help="segmentation loss: BCEWithLogits (the reference's train()), Dice, bce_weight * BCE + dice_weight * Dice "
-                         "(the reference's DiceLoss / CombinedLoss, clip_seg_finetuner.py:40-74), or the Lovasz hinge (Berman et al. 2018)")
+                         "(the reference's DiceLoss / CombinedLoss, clip_seg_finetuner.py:40-74), the Lovasz hinge (Berman et al. 2018), "
+                         "the Tversky loss (Salehi et al. 2017), the focal-Tversky loss (Abraham & Khan 2019), or focal_weight * focal "
+                         "(Lin et al. 2017) + tversky_weight * Dice (mi355.nn.FocalTverskyLoss; the focal loss alone: focal_dice with "
+                         "--focal-weight 1 --tversky-weight 0)")
     ap.add_argument("--bce-weight", type=float, default=0.5, help="bce_dice: weight of the BCE term")
     ap.add_argument("--dice-weight", type=float, default=0.5, help="bce_dice: weight of the Dice term")
     ap.add_argument("--dice-per-sample", action="store_true", help="Dice term per image, averaged over the batch (default: over the whole batch)")
+    ap.add_argument("--focal-gamma", type=float, default=2.0, help="focal_dice, --cls-loss focal: the focusing exponent (0: none)")
+    ap.add_argument("--focal-alpha", type=float, default=0.25, help="focal_dice: weight of the positive pixels, 1 - alpha of the others; -1 = off")
+    ap.add_argument("--tversky-alpha", type=float, default=0.7, help="tversky, focal_tversky: weight of the false positives")
+    ap.add_argument("--tversky-beta", type=float, default=0.3, help="tversky, focal_tversky: weight of the false negatives (beta > alpha favours recall)")
+    ap.add_argument("--tversky-exponent", type=float, default=0.75, help="focal_tversky: (1 - TI)^exponent; 0.75 is Abraham & Khan's gamma = 4/3")
+    ap.add_argument("--focal-weight", type=float, default=0.5, help="focal_dice: weight of the focal term")
+    ap.add_argument("--tversky-weight", type=float, default=0.5, help="focal_dice: weight of the Dice term")
+    ap.add_argument("--cls-loss", choices=["ce", "focal"], default="ce",
+                    help="cls: cross-entropy with label smoothing 0.1 (the reference's train()) or the focal cross-entropy "
+                         "(mi355.nn.FocalCrossEntropyLoss(--focal-gamma), weighted by --class-weight balanced when given)")
     ap.add_argument("--boundary-weight", type=float, default=0.0,
                     help="weight of the boundary loss (Kervadec et al. 2019) added to --seg-loss; 0 = off")
     ap.add_argument("--boundary-schedule", choices=["constant", "rebalance"], default="constant",
@@ -204,18 +223,72 @@ def balanced_class_weights(labels, n_classes):
 
 def cls_criterion(args, batch_mix, dataset=None, indices=None, say=print):
     """The classifier's loss: None = train()'s own default (CrossEntropyLoss(0.1), or MixCrossEntropyLoss(0.1) on mixed batches);
-    with --class-weight balanced MixCrossEntropyLoss(0.1, weight) from the labels of ``dataset.samples`` at ``indices``."""
-    if args.class_weight == "none":
-        return None
-    if dataset is None or not hasattr(dataset, "samples"):
-        say("--class-weight balanced needs the file list of --data-root: ignored for synthetic data")
+    with --class-weight balanced MixCrossEntropyLoss(0.1, weight) from the labels of ``dataset.samples`` at ``indices``.  With
+    --cls-loss focal: FocalCrossEntropyLoss(--focal-gamma, that weight or None) (cls_loss_arg has checked the flags)."""
+    focal = cls_loss_arg(args)
+    w = None
+    if args.class_weight != "none":
+        if dataset is None or not hasattr(dataset, "samples"):
+            say("--class-weight balanced needs the file list of --data-root: ignored for synthetic data")
+        else:
+            from utils.helpers import CLASSES
+            idx = range(len(dataset.samples)) if indices is None else indices
+            w = balanced_class_weights([dataset.samples[i][1] for i in idx], len(CLASSES))
+            say(f"class weights (balanced): {', '.join(f'{c} {v:.3f}' for c, v in zip(CLASSES, w))}")
+    if focal:
+        from mi355 import nn as mnn
+        return mnn.FocalCrossEntropyLoss(gamma=args.focal_gamma, weight=w)
+    if w is None:
         return None
     from mi355 import nn as mnn
-    from utils.helpers import CLASSES
-    idx = range(len(dataset.samples)) if indices is None else indices
-    w = balanced_class_weights([dataset.samples[i][1] for i in idx], len(CLASSES))
-    say(f"class weights (balanced): {', '.join(f'{c} {v:.3f}' for c, v in zip(CLASSES, w))}")
     return mnn.MixCrossEntropyLoss(label_smoothing=0.1, weight=w)
+
+
+def cls_loss_arg(args):
+    """--cls-loss: False for ce (today's criterion), True for focal, after a clear error for what the focal cross-entropy cannot be
+    combined with — raised here, before any data is read."""
+    if args.cls_loss != "focal":
+        return False
+    if args.task == "seg":
+        raise ValueError("--cls-loss focal is for classifiers (--task cls or both); the segmenters take --seg-loss focal_dice")
+    bad = [flag for flag, v in (("--mixup-alpha", args.mixup_alpha), ("--cutmix-alpha", args.cutmix_alpha)) if v != 0]
+    if bad:
+        raise ValueError(f"--cls-loss focal: {', '.join(bad)} {'gives' if len(bad) == 1 else 'give'} two labels per sample, the focal "
+                         "cross-entropy is defined for one true class; train mixed batches with --cls-loss ce")
+    if not (args.focal_gamma >= 0 and args.focal_gamma != float("inf")):
+        raise ValueError(f"--focal-gamma must be a finite number >= 0 ({args.focal_gamma})")
+    return True
+
+
+def focal_arg(args):
+    """--seg-loss tversky | focal_tversky | focal_dice: None for the other losses, else the keyword arguments of
+    mi355.nn.FocalTverskyLoss, after a clear error for the terms these losses are not combined with and for values out of range —
+    raised here, before any data is read.  (--seg-classes > 1 next to them is multiclass_arg's error.)"""
+    if args.seg_loss not in FOCAL_SEG_LOSSES:
+        return None
+    bad = [flag for flag, on in (("--boundary-weight", args.boundary_weight != 0), ("--lovasz-weight", args.lovasz_weight != 0)) if on]
+    if bad:
+        raise ValueError(f"--seg-loss {args.seg_loss}: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} added to --seg-loss "
+                         "bce|dice|bce_dice only")
+    fin = float("inf")
+    if not (args.focal_gamma >= 0 and args.focal_gamma != fin):
+        raise ValueError(f"--focal-gamma must be a finite number >= 0 ({args.focal_gamma})")
+    if not (args.focal_alpha <= 1 and args.focal_alpha != -fin):
+        raise ValueError(f"--focal-alpha must lie in [0, 1], or be negative (-1) for no class balance ({args.focal_alpha})")
+    if not (args.tversky_alpha >= 0 and args.tversky_beta >= 0 and 0 < args.tversky_alpha + args.tversky_beta < fin):
+        raise ValueError(f"--tversky-alpha and --tversky-beta must be finite, not negative and not both 0 ({args.tversky_alpha}, {args.tversky_beta})")
+    if not 0 < args.tversky_exponent < fin:
+        raise ValueError(f"--tversky-exponent must be a finite number > 0 ({args.tversky_exponent})")
+    if not (0 <= args.focal_weight < fin and 0 <= args.tversky_weight < fin):
+        raise ValueError(f"--focal-weight and --tversky-weight must be finite and not negative ({args.focal_weight}, {args.tversky_weight})")
+    focal = dict(focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma)
+    tversky = dict(alpha=args.tversky_alpha, beta=args.tversky_beta, per_sample=args.dice_per_sample)
+    if args.seg_loss == "tversky":
+        return dict(focal_weight=0.0, tversky_weight=1.0, exponent=1.0, **tversky)
+    if args.seg_loss == "focal_tversky":
+        return dict(focal_weight=0.0, tversky_weight=1.0, exponent=args.tversky_exponent, **tversky)
+    return dict(focal_weight=args.focal_weight, tversky_weight=args.tversky_weight, alpha=0.5, beta=0.5, exponent=1.0,
+                per_sample=args.dice_per_sample, **focal)
 
 
 def multiclass_arg(args):
@@ -228,7 +301,8 @@ def multiclass_arg(args):
         raise ValueError(f"--seg-classes must lie in [1, 16] ({k})")
     if args.task != "seg":
         raise ValueError(f"--seg-classes {k} is for --task seg (got --task {args.task})")
-    bad = [flag for flag, on in (("--seg-loss lovasz", args.seg_loss == "lovasz"), ("--boundary-weight", args.boundary_weight != 0),
+    bad = [flag for flag, on in (("--seg-loss lovasz", args.seg_loss == "lovasz"),
+                                 (f"--seg-loss {args.seg_loss}", args.seg_loss in FOCAL_SEG_LOSSES), ("--boundary-weight", args.boundary_weight != 0),
                                  ("--lovasz-weight", args.lovasz_weight != 0), ("--cutmix-alpha", args.cutmix_alpha != 0),
                                  ("--mixup-alpha", args.mixup_alpha != 0), ("--calibrate", args.calibrate)) if on]
     if bad:
@@ -259,6 +333,10 @@ def seg_criterion(args):
     if mc is not None:
         from mi355 import nn as mnn
         return mnn.MultiClassSegLoss(**mc)
+    ftv = focal_arg(args)
+    if ftv is not None:
+        from mi355 import nn as mnn
+        return mnn.FocalTverskyLoss(**ftv)
     if args.boundary_weight < 0:
         raise ValueError(f"--boundary-weight must not be negative ({args.boundary_weight})")
     if args.lovasz_weight < 0:
@@ -317,6 +395,9 @@ def main():
     tasks = ["cls", "seg"] if args.task == "both" else [args.task]
     mixes = {task: mix_arg(args, task, rank) for task in tasks}          # (a bad flag fails before any data is read)
     multi = multiclass_arg(args) is not None
+    if not multi and "seg" in tasks:
+        focal_arg(args)
+    cls_loss_arg(args)
     seg_labels = {"labels": True} if multi else {}
     for task in tasks:
         names = [args.model] if args.model else (CLS_MODELS if task == "cls" else SEG_MODELS)
