@@ -692,6 +692,40 @@ int mi355_amp_update(float* scale, float* inv_scale, int32_t* growth_tracker, co
                      float backoff, int interval, mi355_stream_t s);
 int mi355_fill_f32(float* p, float v, long long n, mi355_stream_t s);
 
+/* ---- weight averaging along the optimiser trajectory (mi355/averaging.py; nothing in the reference): EMA (Mean Teacher, timm's
+ * ModelEmaV2) and the equal-weight average of SWA (Izmailov et al. 2018) over flat fp32 buffers.  With t = count[0], the number
+ * of updates INCLUDING this one (the caller ticks it first with mi355_step_tick under the same found_inf):
+ *   mode 0 (EMA):   d = warmup > 0 ? min(decay, (1 + t) / (warmup + t)) : decay;  a = 1 - d     (timm's warm-up of the decay)
+ *   mode 1 (equal): a = 1 / t;  t == 1 COPIES p (avg + 1 * (p - avg) is not p in floating point)
+ * a is formed in double (decay and warmup widened first) and rounded to float once.  Then, in fp32, every operation rounded on
+ * its own (no FMA) and nothing atomic:
+ *   diff = p[i] - avg[i];   avg[i] = diff == 0 ? avg[i] : avg[i] + a * diff
+ * (the select keeps avg's bits where p equals it: -0 + a * +0 would be +0; padding and frozen parameters therefore never move).
+ * Nothing is written when found_inf != NULL && found_inf[0] != 0 (AdamW skipped that step; mi355_step_tick did not count it), or
+ * when t < 1.  tests/averaging_ref.py restates all of it in numpy float32; the same input gives the same bytes. ------------- */
+/* One flat range of n floats.  16-byte accesses where avg and p share their offset within 16 bytes, between a scalar head up to
+ * the first 16-byte boundary and a scalar tail; scalar throughout otherwise.  avg == p or disjoint ranges; n == 0: OK, no launch.
+ * 12 bytes of traffic per element. */
+int mi355_avg_update(float* avg, const float* p, long long n, int mode, float decay, float warmup, const int32_t* count,
+                     const float* found_inf, mi355_stream_t s);
+/* Elements one sweep of mi355_avg_update's grid covers on the 16-byte path (a longer range is strided): for tests of the stride. */
+int mi355_avg_update_grid_elems(void);
+/* The same arithmetic over `rows` rows {avg pointer, p pointer, n} of three int64 words each, held in DEVICE memory (the
+ * BatchNorm running_mean / running_var buffers of a model: one launch for all of them).  Each row picks the 16-byte or the
+ * scalar path from its own two pointers; a row with n <= 0 or a null pointer is skipped.  0 <= rows <= 65535; rows == 0: OK,
+ * no launch.  Rows must not overlap one another. */
+int mi355_avg_update_table(const int64_t* table, int rows, int mode, float decay, float warmup, const int32_t* count,
+                           const float* found_inf, mi355_stream_t s);
+/* dst[i] <-> src[i] for every row {dst pointer, src pointer, n} of such a table (fp32 words moved as they are: any bit pattern
+ * survives); rows must not overlap one another or themselves (dst == src: skipped).  Swapping twice is the identity. */
+int mi355_swap_table(const int64_t* table, int rows, mi355_stream_t s);
+/* Bias correction of BatchNorm running statistics that were accumulated from ZERO with mi355_bn_finalize's recurrence
+ * r = (1 - momentum) r + momentum b: rows {running pointer (fp32 [C]), nbt pointer (int64 [1]), C}; with k = *nbt,
+ *   running[c] = (float)(running[c] / (1 - (1 - momentum)^k))     in double, momentum widened first
+ * which makes running the exponentially weighted MEAN of the k batch statistics.  k == 0 leaves the row untouched (that
+ * BatchNorm never ran).  0 < momentum <= 1. */
+int mi355_bn_debias_table(const int64_t* table, int rows, float momentum, mi355_stream_t s);
+
 /* AdaptiveAvgPool2d((OH,OW)) + Flatten of the torchvision VGG head (helpers.py:158-166 loads `vgg16_bn`):
  * NHWC `dtype` activations -> fp32 [N][C*OH*OW] in NCHW flatten order; backward writes (does not accumulate) dx. */
 int mi355_adaptive_avgpool_fwd(const void* x, int ldx, float* y, int N, int H, int W, int C, int OH, int OW, int dtype,

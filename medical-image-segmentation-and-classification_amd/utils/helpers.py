@@ -13,6 +13,11 @@ Additions the reference does not have, all off by default: ``criterion=`` (a los
 validation loss) and a ``utils.mix.MixedBatches(train_dl, batch_mix)`` in the place of ``train_dl`` (the parameter list stays the
 reference's plus ``criterion``): mixup / CutMix of every training batch on the device by that ``utils.mix.BatchMix``; classifiers then
 train against a ``MixedTarget`` with ``mi355.nn.MixCrossEntropyLoss``, validation stays on hard labels and unmixed batches.
+A ``mi355.averaging.WithAveraging(train_dl, averaging)`` in the place of ``train_dl`` (outside a ``MixedBatches``, if both are used;
+the parameter list stays as it is here too), ``averaging`` a dict such as ``{"mode": "ema", "decay": 0.999, "warmup": 10}`` or
+``{"mode": "swa", "swa_start": E}``, or a ``mi355.averaging.WeightAverage``: an average of the weights along the trajectory, validated
+and saved beside the raw model (``{name}_ema_best_loss.pt`` / ``{name}_ema_best_acc.pt``, ``{name}_swa.pt``); the raw model's lines,
+schedule and files do not change.
 
 Data parallel: when ``torch.distributed`` is initialised with more than one rank (``torchrun --nproc-per-node N
 utils/trainer.py ...``), ``train()`` shards the loaders' batches by rank (utils/distributed.py), wraps the model in
@@ -123,8 +128,35 @@ def _make_optimizer(params, lr):
     return moptim.AdamW(params, lr=lr, weight_decay=5e-4)
 
 
+def _averaging_spec(averaging, epochs):
+    """WithAveraging(train_dl, averaging).averaging -> (WeightAverage or its constructor arguments, mode, first SWA epoch); validated before any work"""
+    from mi355.averaging import WeightAverage
+    if isinstance(averaging, WeightAverage):
+        return averaging, averaging.mode, max(1, int(math.ceil(0.75 * epochs)))
+    if not isinstance(averaging, dict):
+        raise TypeError(f"averaging must be None, a dict or a mi355.averaging.WeightAverage (got {type(averaging).__name__})")
+    spec = dict(averaging)
+    mode = spec.setdefault("mode", "ema")
+    swa_start = spec.pop("swa_start", None)
+    unknown = set(spec) - {"mode", "decay", "warmup", "buffers"}
+    if unknown or mode not in ("ema", "swa"):
+        raise ValueError(f"averaging: mode 'ema' or 'swa' with decay / warmup / buffers / swa_start (got {averaging})")
+    if swa_start is None:
+        swa_start = max(1, int(math.ceil(0.75 * epochs)))          # an epoch, 1-based: the last quarter of the run
+    if mode == "swa" and not 1 <= int(swa_start) <= epochs:
+        raise ValueError(f"averaging: swa_start {swa_start} outside the epochs 1..{epochs}")
+    return spec, mode, int(swa_start)
+
+
 def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False, cls_head_name=None, criterion=None):
     device = torch.device(device)
+    # train_dl may be a mi355.averaging.WithAveraging(loader, averaging): the loader is used as it would be without the wrapper and
+    # an average of the weights is kept beside the raw model (below); a plain loader = today's loop
+    averaging = None
+    if hasattr(train_dl, "averaging"):
+        train_dl, averaging = train_dl.loader, train_dl.averaging
+        if averaging is not None:
+            averaging, avg_mode, swa_start = _averaging_spec(averaging, epochs)
     model = model.to(device)
     if hasattr(model, "engine"):
         model.engine._check_storage()                 # flat fp32 parameter / gradient buffers
@@ -135,6 +167,8 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
     batch_mix = None
     if hasattr(train_dl, "batch_mix"):
         train_dl, batch_mix = train_dl.loader, train_dl.batch_mix
+    if hasattr(train_dl, "averaging"):
+        raise TypeError("WithAveraging goes OUTSIDE MixedBatches: train(model, WithAveraging(MixedBatches(loader, batch_mix), averaging), ...)")
     if batch_mix is not None:
         if bool(getattr(batch_mix, "seg", seg)) != bool(seg):
             raise ValueError(f"batch_mix was built with seg={batch_mix.seg} but train() runs with seg={seg}")
@@ -187,6 +221,59 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
     patience, stale = 10, 0
     t0 = time.time()
 
+    # averaging (None = off): an EMA of the weights updated after every optimiser step, or the equal-weight SWA average of the
+    # epoch ends from swa_start on (mi355/averaging.py).  The raw model is trained, validated, logged, scheduled and saved exactly
+    # as without it; the averaged model gets one more validation pass and files of its own.  It is created behind the
+    # data-parallel wrapper, so that every rank averages the PARAMETERS of the replica it shares with rank 0 (the averaged buffers
+    # are per rank between validations: validate_averaged syncs them).
+    avg = None
+    if averaging is not None:
+        from mi355.averaging import WeightAverage, update_bn
+        avg = averaging if isinstance(averaging, WeightAverage) else WeightAverage(model, **averaging)
+        avg_best = float("inf") if seg else 0.0
+
+    def validate():
+        """one pass over val_dl in eval mode -> (loss sum, metric sum) on the device"""
+        model.eval()
+        vloss = torch.zeros((), device=device)
+        vmetric = torch.zeros((), device=device)
+        with torch.no_grad():
+            for x, y in val_dl:
+                x, y = x.to(device), y.to(device)
+                out = model(x)
+                if seg and out.dim() == 3:
+                    out = out.unsqueeze(1)
+                vloss += criterion(out, y) * x.size(0)
+                if seg and hasattr(criterion, "val_metric"):
+                    vmetric += criterion.val_metric(out, y)      # multi-class criteria: mean IoU from the confusion matrix
+                elif seg:
+                    vmetric += _iou_device(out.float(), y.float(), 0.5, is_logit=True)
+                else:
+                    vmetric += (torch.argmax(out, 1) == y).sum()
+        return vloss, vmetric
+
+    def validate_averaged(refresh_bn):
+        """validate() of the averaged model, inside swap() -> (val loss, metric as printed, its state_dict on rank 0).  The host
+        random state is put back afterwards: a DataLoader draws its base seed from it whenever it is iterated, and the next
+        epoch's shuffle must be the one a run without averaging sees."""
+        rng = torch.get_rng_state()
+        with avg.swap():
+            if refresh_bn:
+                update_bn(model, train_dl, device)               # the plain training loader: no batch_mix
+            if dp is not None:
+                # BatchNorm statistics are per GPU: the averaged ones were folded from (EMA) or re-estimated on (SWA: train_dl is
+                # this rank's shard) each rank's own.  The live buffers ARE the averaged ones in here, so rank 0's go to every
+                # rank, as before the raw validation: all ranks validate, and rank 0 saves, ONE averaged model.  The synced
+                # statistics stay with the average on exit.
+                dp.sync_buffers()
+            vl, vm = validate()
+            if dp is not None:
+                vl, vm = all_reduce_sums(vl, vm)
+            sd = model.state_dict() if rank == 0 else None
+            sd = {k: v.detach().clone() for k, v in sd.items()} if sd is not None else None
+        torch.set_rng_state(rng)
+        return vl.item() / n_val, (vm.item() / n_val_batches if seg else 100 * vm.item() / n_val), sd
+
     for epoch in range(1, epochs + 1):
         if hasattr(criterion, "on_epoch"):
             criterion.on_epoch(epoch - 1, epochs)     # epoch-dependent loss weights (mnn.RegionBoundaryLoss), index from 0
@@ -216,6 +303,8 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
             scaler.unscale_(optimizer)
             moptim.clip_grad_norm_(model.parameters(), max_norm=1.0, inv_scale=inv_scale)
             scaler.step(optimizer)
+            if avg is not None and avg_mode == "ema":
+                avg.update(optimizer)                 # one streaming launch; skips with the optimiser on inf / nan gradients
             scaler.update()
             loss_sum += loss.detach() * x.size(0)
             seen_all += x.size(0)
@@ -225,22 +314,7 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
 
         if dp is not None:
             dp.sync_buffers()                         # rank 0's BatchNorm statistics everywhere: one model is validated and saved
-        model.eval()
-        vloss = torch.zeros((), device=device)
-        vmetric = torch.zeros((), device=device)
-        with torch.no_grad():
-            for x, y in val_dl:
-                x, y = x.to(device), y.to(device)
-                out = model(x)
-                if seg and out.dim() == 3:
-                    out = out.unsqueeze(1)
-                vloss += criterion(out, y) * x.size(0)
-                if seg and hasattr(criterion, "val_metric"):
-                    vmetric += criterion.val_metric(out, y)      # multi-class criteria: mean IoU from the confusion matrix
-                elif seg:
-                    vmetric += _iou_device(out.float(), y.float(), 0.5, is_logit=True)
-                else:
-                    vmetric += (torch.argmax(out, 1) == y).sum()
+        vloss, vmetric = validate()
 
         # one host read-back per epoch (data parallel: one collective over the five accumulators first; the padded last
         # optimiser step makes the number of samples trained on larger than the dataset, so the mean divides by what was seen)
@@ -277,9 +351,40 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
                 torch.save(model.state_dict(), os.path.join(save_dir, fname))
         else:
             stale += 1
+
+        if avg is not None and avg_mode == "ema":
+            # the averaged model of this epoch: validated inside swap(), logged on a line of its own, saved on its own best score
+            a_loss, a_metric, a_sd = validate_averaged(False)
+            if seg:
+                say(f"[{name}] Ep{epoch}: EMA ValLoss {a_loss:.3f} | IoU {a_metric:.3f}")
+            else:
+                say(f"[{name}] Ep{epoch}: EMA ValLoss {a_loss:.3f} | ValAcc {a_metric:.2f}%")
+            if (a_loss < avg_best) if seg else (a_metric > avg_best):
+                avg_best = a_loss if seg else a_metric
+                if rank == 0:
+                    os.makedirs(save_dir, exist_ok=True)
+                    torch.save(a_sd, os.path.join(save_dir, f"{name}_ema_best_loss.pt" if seg else f"{name}_ema_best_acc.pt"))
+        elif avg is not None and epoch >= swa_start:
+            avg.update()                              # SWA: the iterate at the end of this epoch joins the equal-weight average
+
         if stale >= patience:
             say(f"Early stopping at epoch {epoch}. Best score: {best_score:.2f}")
             break
+
+    if avg is not None and avg_mode == "swa":
+        n_avg = int(avg.count.item())
+        if n_avg == 0:
+            say(f"[{name}] SWA: training stopped before epoch {swa_start}, nothing was averaged")
+        else:
+            # BatchNorm statistics of the averaged weights do not exist yet: re-estimate them on the training loader, then validate
+            a_loss, a_metric, a_sd = validate_averaged(True)
+            if seg:
+                say(f"[{name}] SWA ({n_avg} epochs): ValLoss {a_loss:.3f} | IoU {a_metric:.3f}")
+            else:
+                say(f"[{name}] SWA ({n_avg} epochs): ValLoss {a_loss:.3f} | ValAcc {a_metric:.2f}%")
+            if rank == 0:
+                os.makedirs(save_dir, exist_ok=True)
+                torch.save(a_sd, os.path.join(save_dir, f"{name}_swa.pt"))
 
     say(f"Training for {name} finished in {(time.time() - t0) / 60:.2f} minutes.")
     return best_score

@@ -548,6 +548,19 @@ _CLS_FILES = {"ResNet18": "ResNet18_best_acc.pt", "ResNet50": "ResNet50_best_acc
               "VGG19": "VGG19_best_acc.pt", "CLIP": "CLIP_best_acc.pt"}
 _SEG_FILES = {"ResNetUnet": "ResNetUnet_best_loss.pt", "AttentionUNet": "AttentionUNet_best_loss.pt",
               "R2Unet": "R2Unet_best_loss.pt", "R2AttUnet": "R2AttUnet_best_loss.pt", "CLIPSeg": "CLIPSeg_best_loss.pt"}
+WEIGHTS_VARIANTS = ("raw", "ema", "swa")
+
+
+def variant_files(files, variant):
+    """_CLS_FILES / _SEG_FILES for a weights variant: "raw" is the table itself; "ema" / "swa" name the averaged checkpoints
+    train(model, WithAveraging(train_dl, ...), ...) writes beside the raw ones ({name}_ema_best_acc.pt / {name}_ema_best_loss.pt, {name}_swa.pt)."""
+    if variant not in WEIGHTS_VARIANTS:
+        raise ValueError(f"weights_variant must be one of {WEIGHTS_VARIANTS}, got {variant!r}")
+    if variant == "raw":
+        return files
+    if variant == "ema":
+        return {m: f.replace("_best_", "_ema_best_") for m, f in files.items()}
+    return {m: f.rsplit("_best_", 1)[0] + "_swa.pt" for m, f in files.items()}
 
 
 def check_multiclass_options(seg_classes, surface=False, tta=None, sliding=None, auc=False, ci=None, calibration=None):
@@ -611,7 +624,7 @@ def _multiclass_lines(r):
 
 def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=None, cls_weights_dir=None,
                     seg_weights_dir=None, clahe=None, tta=None, tta_merge="prob", sliding=None, size=None, ci=None, calibration=None,
-                    seg_classes=1, seg_ignore_index=255, class_names=None, auc=False, calibration_bins=15, surface=False):
+                    seg_classes=1, seg_ignore_index=255, class_names=None, weights_variant="raw", auc=False, calibration_bins=15, surface=False):
     """Evaluate every checkpoint found under the weights directories (tester.py:513-735): same model names, file
     names, skip rules and result dictionary.  Like the reference (:531-555, :569-580, :651-666) the test loaders are built
     from ``DATA_ROOT/splits/test.csv`` with the validation transforms — here `utils.dataset` + `GpuBatchLoader` (native PNG
@@ -638,8 +651,13 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
     FileNotFoundError naming the file.
     ``seg_classes`` K > 1 (with ``seg_ignore_index``, ``class_names``): the segmenters are built with K-channel heads, the default
     segmentation loader yields class-index masks (SegmentationDataset(labels=True)) and every segmenter goes through
-    evaluate_multiclass_segmentation_model; the binary-only options (check_multiclass_options) raise ValueError."""
+    evaluate_multiclass_segmentation_model; the binary-only options (check_multiclass_options) raise ValueError.
+    ``weights_variant`` "ema" / "swa": the averaged checkpoints of train(model, WithAveraging(train_dl, ...), ...) are tested in place of the raw ones
+    (variant_files); a model without such a file is skipped like any model without weights.  Pass it BY KEYWORD: it stands in front
+    of ``auc`` / ``calibration_bins`` / ``surface`` in the parameter list (tests pin those three as its tail), so a positional call
+    that reaches past ``class_names`` would shift; a value that is not one of the three names raises ValueError."""
     from utils.helpers import get_class_model, get_seg_model
+    cls_files, seg_files = variant_files(_CLS_FILES, weights_variant), variant_files(_SEG_FILES, weights_variant)
     seg_classes = check_multiclass_options(seg_classes, surface, tta, sliding, auc, ci, calibration)
     ci = _check_ci(ci)
     size = IMG_SIZE if size is None else int(size)
@@ -679,7 +697,9 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
                 continue
             if calibration is not None:
                 from utils.calibrate import find_sidecar
-                cals[model_name] = find_sidecar(calibration, model_name, n_samples_label.lower() + "_models")
+                # (an averaged checkpoint has a sidecar of its own, {name}_{variant}_calibration.json: trainer.py --calibrate)
+                tag = model_name if weights_variant == "raw" else f"{model_name}_{weights_variant}"
+                cals[model_name] = find_sidecar(calibration, tag, n_samples_label.lower() + "_models")
             try:
                 model = build(model_name)
                 model.load_state_dict(torch.load(weight_path, map_location=device))
@@ -725,7 +745,7 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
             cls_test = lambda m, l, d, name: evaluate_classification_model(m, l, d, name, tta=tta, auc=auc, calibration_bins=calibration_bins, ci=ci)  # noqa: E731
         if calibration is not None:
             cls_test = lambda m, l, d, name: evaluate_classification_model(m, l, d, name, tta=tta, auc=auc, calibration_bins=calibration_bins, ci=ci, calibration=cals[name])  # noqa: E731
-        run(_CLS_FILES, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], cls_test, "Classification")
+        run(cls_files, cls_weights_dir, cls_loader, lambda n: get_class_model(n)[0], cls_test, "Classification")
     if seg_loader is None:
         print(f"\n[WARNING] Segmentation test dataset not found: no loader given for {DATA_ROOT!r}")
         print("Skipping segmentation model testing...")
@@ -764,7 +784,7 @@ def test_all_models(device="cuda", batch_size=16, cls_loader=None, seg_loader=No
         if seg_classes > 1:
             seg_build = lambda n: get_seg_model(n, classes=seg_classes)  # noqa: E731
             seg_test = lambda m, l, d, name: evaluate_multiclass_segmentation_model(m, l, d, name, seg_classes, seg_ignore_index, class_names)  # noqa: E731
-        run(_SEG_FILES, seg_weights_dir, seg_loader, seg_build, seg_test, "Segmentation")
+        run(seg_files, seg_weights_dir, seg_loader, seg_build, seg_test, "Segmentation")
     return results
 
 
@@ -975,6 +995,9 @@ def build_parser():
                           "255 = ignore): per-class and mean Dice / IoU, pixel accuracy and the confusion matrix (utils/multiclass.py)")
     _ap.add_argument("--seg-ignore-index", type=int, default=255, help="--seg-classes: the label left out of every count (-1: none)")
     _ap.add_argument("--class-names", default=None, help="--seg-classes: comma-separated names of the K classes, in class order")
+    _ap.add_argument("--weights-variant", choices=WEIGHTS_VARIANTS, default="raw",
+                     help="which checkpoint of every model to test: raw = {name}_best_*.pt; ema / swa = the averaged weights written by "
+                          "trainer.py --ema-decay / --swa-start ({name}_ema_best_*.pt, {name}_swa.pt)")
     return _ap
 
 
@@ -1014,6 +1037,8 @@ if __name__ == "__main__":          # python utils/tester.py (tester.py:879-898)
         _kw["ci"] = CI(_args.ci, _args.ci_level, _args.ci_seed)
     if _args.calibration is not None:
         _kw["calibration"] = _args.calibration
+    if _args.weights_variant != "raw":
+        _kw["weights_variant"] = _args.weights_variant
     results = test_all_models(device="cuda", batch_size=16, **_kw)
     print_summary(results)
     if _args.ci != 0:

@@ -150,20 +150,58 @@ def build_parser():
                     help="after training, fit the post-hoc calibration of the best checkpoint on the validation split (utils/calibrate.py): "
                          "a classifier's temperature, a segmenter's Dice-optimal mask threshold; written next to the checkpoint as "
                          "{name}_calibration.json for tester.py --calibration and JointPipeline(calibration=...)")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights with this decay (usual value 0.999; mi355/averaging.py): "
+                         "validated on a line of its own every epoch and saved as {name}_ema_best_loss.pt / {name}_ema_best_acc.pt "
+                         "(tester.py --weights-variant ema); off by default")
+    ap.add_argument("--ema-warmup", type=float, default=10.0,
+                    help="--ema-decay: the decay in force at update t is min(decay, (1 + t) / (warmup + t)); 0 = the plain decay")
+    ap.add_argument("--swa-start", type=int, default=None,
+                    help="stochastic weight averaging: the equal-weight average of the weights at the end of every epoch from this one "
+                         "(1-based) on, BatchNorm statistics re-estimated on the training data, saved as {name}_swa.pt "
+                         "(tester.py --weights-variant swa); off by default; not together with --ema-decay")
     return ap
 
 
-def calibrate_checkpoint(model, val_dl, device, name, save_dir, seg, say=print):
+def averaging_arg(args):
+    """What train() takes as mi355.averaging.WithAveraging(train_dl, ...): None without --ema-decay / --swa-start (today's loop), else the dict it takes, after a
+    clear error for both at once and for values out of range — raised here, before any data is read."""
+    if args.ema_decay is not None and args.swa_start is not None:
+        raise ValueError("--ema-decay and --swa-start are mutually exclusive: one average of the weights per run")
+    if args.ema_decay is not None:
+        if not 0 <= args.ema_decay < 1:
+            raise ValueError(f"--ema-decay must lie in [0, 1) ({args.ema_decay})")
+        if not (args.ema_warmup >= 0 and args.ema_warmup != float("inf")):
+            raise ValueError(f"--ema-warmup must be a finite number >= 0 ({args.ema_warmup})")
+        return {"mode": "ema", "decay": args.ema_decay, "warmup": args.ema_warmup}
+    if args.swa_start is not None:
+        if not 1 <= args.swa_start <= args.epochs:
+            raise ValueError(f"--swa-start must be an epoch in [1, --epochs = {args.epochs}] ({args.swa_start})")
+        return {"mode": "swa", "swa_start": args.swa_start}
+    return None
+
+
+AVERAGED_FILES = {"ema": ("{name}_ema_best_loss.pt", "{name}_ema_best_acc.pt"), "swa": ("{name}_swa.pt", "{name}_swa.pt")}
+
+
+def calibrate_checkpoint(model, val_dl, device, name, save_dir, seg, say=print, variant=None):
     """--calibrate: reload ``name``'s best checkpoint from ``save_dir`` into ``model``, fit its calibration on ``val_dl`` (rank 0; the
-    other ranks skip) and write the sidecar next to the checkpoint -> the Calibration, or None on the other ranks."""
+    other ranks skip) and write the sidecar next to the checkpoint -> the Calibration, or None on the other ranks.  ``variant``
+    "ema" / "swa": the averaged checkpoint instead, when train() wrote one (None otherwise); its sidecar is {name}_{variant}_calibration.json."""
     from utils.calibrate import Calibration, calibrate_model
     from utils.distributed import dist_info
     if dist_info()[0] != 0:
         return None
-    model.load_state_dict(torch.load(os.path.join(save_dir, f"{name}_best_loss.pt" if seg else f"{name}_best_acc.pt"), map_location=device))
+    fname = f"{name}_best_loss.pt" if seg else f"{name}_best_acc.pt"
+    if variant is not None:
+        fname = AVERAGED_FILES[variant][0 if seg else 1].format(name=name)
+        if not os.path.exists(os.path.join(save_dir, fname)):
+            return None
+    model.load_state_dict(torch.load(os.path.join(save_dir, fname), map_location=device))
     cal = calibrate_model(model.to(device), val_dl, device, seg)
-    path = cal.save(Calibration.path(save_dir, name))
-    say(f"[calibration] {name}: {cal.describe()} -> {path}")
+    tag = name if variant is None else f"{name}_{variant}"
+    path = cal.save(Calibration.path(save_dir, tag))
+    say(f"[calibration] {tag}: {cal.describe()} -> {path}")
     return cal
 
 
@@ -398,6 +436,8 @@ def main():
     if not multi and "seg" in tasks:
         focal_arg(args)
     cls_loss_arg(args)
+    averaging = averaging_arg(args)
+    variant = None if averaging is None else averaging["mode"]
     seg_labels = {"labels": True} if multi else {}
     for task in tasks:
         names = [args.model] if args.model else (CLS_MODELS if task == "cls" else SEG_MODELS)
@@ -425,6 +465,9 @@ def main():
         if mixes[task] is not None:
             from utils.mix import MixedBatches
             train_dl = MixedBatches(train_dl, mixes[task])
+        if averaging is not None:
+            from mi355.averaging import WithAveraging
+            train_dl = WithAveraging(train_dl, dict(averaging))
         cls_crit = None
         if task == "cls":
             cls_crit = cls_criterion(args, mixes[task], ds_tr if args.data_root else None, perm[:n_train] if args.data_root else None, say)
@@ -436,12 +479,16 @@ def main():
                              seg=False, cls_head_name=head, criterion=cls_crit)
                 if args.calibrate:
                     calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "classification_models"), False, say)
+                    if variant is not None:
+                        calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "classification_models"), False, say, variant)
             else:
                 model = get_seg_model(name, classes=args.seg_classes)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True,
                              criterion=seg_criterion(args))
                 if args.calibrate:
                     calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "segmentation_models"), True, say)
+                    if variant is not None:
+                        calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "segmentation_models"), True, say, variant)
             results[(task, name)] = best
     say("\n===== SUMMARY =====")
     for (task, name), best in results.items():
