@@ -427,6 +427,40 @@ int mi355_ftv_loss_bwd(const float* z, const float* t, int B, long long per, flo
  * outside contributes loss 0 and gradient 0 (z and weight are never indexed by it). */
 int mi355_ce_focal(const float* z, const int64_t* y, const float* weight, float* loss, float* dz, const float* gscale, int B,
                    int C, float gamma, mi355_stream_t s);
+/* Knowledge distillation (Hinton et al. 2015; nothing in the reference): the losses above with a third operand, the logits v of a
+ * frozen teacher, and a temperature T > 0.
+ * Binary segmentation, z, t, v fp32 [B][per], n = B per, a = z / T, b = v / T, p_T = sigmoid(a), q = sigmoid(b), p = sigmoid(z):
+ *   KD      = T^2 (1 / n) sum_i (q_i log(q_i / p_T,i) + (1 - q_i) log((1 - q_i) / (1 - p_T,i))),
+ *             each element formed as softplus(-a) - softplus(-b) + (1 - q)(a - b)
+ *   loss[0] = bce_weight mean(BCEWithLogits(z, t)) + dice_weight Dice(z, t; smooth, per_sample) + kd_weight KD
+ *   loss[1] = the two hard terms alone,  loss[2] = KD (unweighted)
+ *   dz_i    = gscale[0] (bce_weight (p_i - t_i) / n - (a_b t_i - c_b) p_i (1 - p_i) + kd_weight T (p_T,i - q_i) / n)
+ * The Dice term, its per_sample variant, the target (used as it is) and `state` are those of mi355_seg_loss_fwd / _bwd.  p_T and q
+ * come from one device function: v == z gives loss[2] = 0 and loss[0], dz with the bits of the same call with kd_weight = 0.
+ *   mi355_kd_seg_rows: rows of EIGHT floats `partial` must hold (16-byte aligned); a function of (B, per) alone.
+ *   mi355_kd_seg_fwd:  one pass over z, t and v (16-byte accesses when per % 4 == 0 and all three are 16-byte aligned), a
+ *     one-workgroup finalize in double; leaves loss[0 .. 2] and the pair (a_b, c_b) of sample b in state[2 b], state[2 b + 1].
+ *   mi355_kd_seg_bwd:  one pass from the `state` the forward left (same B, per, weights and T); gscale NULL = 1.
+ * kd_weight = 0: v may be NULL and is never read.  Deterministic: no floating-point atomics, every fold in a fixed order; nothing
+ * is allocated and nothing synchronises.  B <= 65535; weights and smooth >= 0; T finite and > 0. */
+int mi355_kd_seg_rows(int B, long long per);
+int mi355_kd_seg_fwd(const float* z, const float* t, const float* v, int B, long long per, float bce_weight, float dice_weight,
+                     float smooth, int per_sample, float kd_weight, float temperature, float* partial, float* state, float* loss,
+                     mi355_stream_t s);
+int mi355_kd_seg_bwd(const float* z, const float* t, const float* v, int B, long long per, float bce_weight, float kd_weight,
+                     float temperature, const float* state, const float* gscale, float* dz, mi355_stream_t s);
+/* Classifiers, z, v fp32 [B][C], hard labels y, t[b][c] = (1 - smoothing) [c == y_b] + smoothing / C:
+ *   hard     = (1 / B) sum_b sum_c weight[c] t[b][c] (-log_softmax(z_b)[c])                 (mi355_ce_mix's hard-label case)
+ *   KD       = T^2 (1 / B) sum_b KL(softmax(v_b / T) || softmax(z_b / T))
+ *   loss[0]  = hard_weight hard + kd_weight KD,  loss[1] = hard,  loss[2] = KD
+ *   dz[b][c] = (gscale[0] / B) (hard_weight (softmax(z_b)[c] sum_k weight[k] t[b][k] - weight[c] t[b][c])
+ *                               + kd_weight T (softmax(z_b / T)[c] - softmax(v_b / T)[c]))
+ * weight NULL: all ones; dz NULL: loss only; gscale NULL: 1; kd_weight = 0: v may be NULL and is never read.  v == z gives
+ * loss[2] = 0.  Evaluated in double (inputs and T widened, exp / log in double) and rounded to float once on store; one workgroup,
+ * thread b % 256 owns row b, then a block fold in a fixed order: bit-reproducible.  Labels only select a class, never index. */
+int mi355_ce_distill(const float* z, const int64_t* y, const float* v, const float* weight, float* loss, float* dz,
+                     const float* gscale, int B, int C, float smoothing, float hard_weight, float kd_weight, float temperature,
+                     mi355_stream_t s);
 /* Multi-class segmentation (nothing in the reference, whose losses and metrics are binary): per-pixel softmax cross-entropy +
  * per-class soft Dice, and the argmax / confusion-matrix pass of the metrics.  Logits z fp32 [N][C][HW] (the NCHW map of the
  * K-channel heads; a plan's dout has the same layout), labels y uint8 [N][HW], 2 <= C <= 16, N <= 65535, HW <= 2^30.

@@ -849,6 +849,185 @@ class FocalCrossEntropyLoss(nn.Module):
         return f"gamma={self.gamma}, weight={None if self.weight is None else self.weight.tolist()}"
 
 
+# ---- knowledge distillation (csrc/distill.hip) ------------------------------------------------------------------------------------
+def _check_kd(kd_weight, temperature):
+    if isinstance(kd_weight, bool) or not 0.0 <= kd_weight <= 1.0:
+        raise ValueError(f"kd_weight must lie in [0, 1] ({kd_weight})")
+    if isinstance(temperature, bool) or not (temperature > 0 and temperature != float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0 ({temperature})")
+
+
+def _teacher_like(out, target):
+    """the teacher logits of a DistillTarget as a contiguous float32 tensor of the student's shape"""
+    v = target.teacher_logits
+
+    def core(shape):          # [N, 1, H, W] and [N, H, W] are the same map
+        return tuple(shape[:1]) + tuple(shape[2:]) if len(shape) == 4 and shape[1] == 1 else tuple(shape)
+
+    if core(v.shape) != core(out.shape):
+        raise ValueError(f"teacher logits {tuple(v.shape)} must match the student's output {tuple(out.shape)}")
+    if v.device != out.device:
+        raise ValueError(f"teacher logits on {v.device}, the student's output on {out.device}")
+    return v.detach().to(torch.float32).contiguous().view(out.shape)
+
+
+class _SegDistillFn(torch.autograd.Function):
+    """BCE + Dice + KD (csrc/distill.hip), the launches of _SegLossFn with the teacher's logits as a third operand: the forward leaves
+    [total, hard, KD] and one coefficient pair per sample on the device, the backward is one pass that reads them with the upstream
+    gradient and writes dL/dlogits."""
+
+    @staticmethod
+    def forward(ctx, out, target, teacher, plan, cfg, holder):
+        if target.dtype != torch.float32 or not target.is_contiguous():
+            target = target.float().contiguous()
+        if target.numel() != out.numel():
+            raise ValueError(f"target size {tuple(target.shape)} must match input size {tuple(out.shape)}")
+        o = out.detach()
+        if not o.is_contiguous():
+            o = o.contiguous()
+        bw, dw, smooth, per_sample, kw, temp = cfg
+        B = o.shape[0]
+        per = o.numel() // B
+        rows = lib.mi355_kd_seg_rows(B, per)
+        if rows <= 0:
+            raise RuntimeError(f"mi355_kd_seg_rows failed: {lib.raw('mi355_last_error')().decode()}")
+        # one buffer: [rows x 8 partial sums | (a_b, c_b) per sample | total, hard, KD]
+        buf = torch.empty(rows * 8 + 2 * B + 3, dtype=torch.float32, device=out.device)
+        partial, state, loss = buf[: rows * 8], buf[rows * 8: rows * 8 + 2 * B], buf[rows * 8 + 2 * B:]
+        lib.mi355_kd_seg_fwd(o, target, teacher, B, per, bw, dw, smooth, 1 if per_sample else 0, kw, temp, partial, state, loss)
+        ctx.o, ctx.t, ctx.v, ctx.plan, ctx.state, ctx.cfg = o, target, teacher, plan, state, cfg
+        holder.last_terms = loss
+        return loss[:1].view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t, plan = ctx.o, ctx.t, ctx.plan
+        bw, _, _, _, kw, temp = ctx.cfg
+        n = o.numel()
+        B = o.shape[0]
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        lib.mi355_kd_seg_bwd(o, t, ctx.v, B, n // B, bw, kw, temp, ctx.state, gs, dz)
+        return dz[:n].view(o.shape), None, None, None, None, None
+
+
+class SegDistillationLoss(nn.Module):
+    """(1 - kd_weight) (bce_weight BCEWithLogits + dice_weight Dice) + kd_weight KD against a ``utils.distill.DistillTarget`` (the hard
+    mask and a frozen teacher's logits v), one autograd node (mi355_kd_seg_*).  With a = z / T, b = v / T:
+
+        KD = T^2 mean_i KL(Bernoulli(sigmoid(b_i)) || Bernoulli(sigmoid(a_i)))        Hinton et al. 2015, per pixel
+
+    The hard terms are ``CombinedLoss``'s (the mask is used as it is).  With a plain mask tensor — the validation loop — the loss is
+    the unscaled hard loss through ``CombinedLoss``'s own launches, bit for bit, so that validation losses stay comparable with an
+    undistilled run.  ``last_terms``: the device tensor [total, hard, KD] of the last distilled call, as the kernel leaves it (no
+    synchronisation): hard is the hard part as it enters the total, (1 - kd_weight) included, KD is unweighted,
+    total = hard + kd_weight KD.  Deterministic: the same input gives the same bits."""
+
+    accepts_mixed_target = False
+    accepts_distill_target = True
+
+    def __init__(self, bce_weight=0.5, dice_weight=0.5, smooth=1.0, per_sample=False, kd_weight=0.5, temperature=2.0):
+        super().__init__()
+        if not (bce_weight >= 0 and dice_weight >= 0 and smooth >= 0):
+            raise ValueError(f"bce_weight, dice_weight and smooth must not be negative ({bce_weight}, {dice_weight}, {smooth})")
+        for name, v in (("bce_weight", bce_weight), ("dice_weight", dice_weight), ("smooth", smooth)):
+            if v == float("inf"):
+                raise ValueError(f"{name} must be finite ({v})")
+        _check_kd(kd_weight, temperature)
+        self.bce_weight, self.dice_weight, self.smooth, self.per_sample = float(bce_weight), float(dice_weight), float(smooth), bool(per_sample)
+        self.kd_weight, self.temperature = float(kd_weight), float(temperature)
+        self.last_terms = None
+
+    def forward(self, out, target):
+        plan = getattr(out, "_mi355_plan", None)
+        if out.dtype != torch.float32:
+            out = out.float()
+        if not hasattr(target, "teacher_logits"):
+            return _SegLossFn.apply(out, target, plan, self.bce_weight, self.dice_weight, self.smooth, self.per_sample)
+        v = _teacher_like(out, target)
+        keep = 1.0 - self.kd_weight
+        cfg = (keep * self.bce_weight, keep * self.dice_weight, self.smooth, self.per_sample, self.kd_weight, self.temperature)
+        return _SegDistillFn.apply(out, target.hard, v, plan, cfg, self)
+
+    def extra_repr(self):
+        return (f"bce_weight={self.bce_weight}, dice_weight={self.dice_weight}, smooth={self.smooth}, per_sample={self.per_sample}, "
+                f"kd_weight={self.kd_weight}, temperature={self.temperature}")
+
+
+class _CEDistillFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, y, teacher, weight, cfg, plan, holder):
+        o = out.detach().contiguous()
+        smoothing, hw, kw, temp = cfg
+        loss = torch.empty(3, dtype=torch.float32, device=out.device)
+        lib.mi355_ce_distill(o, y, teacher, weight, loss, None, None, o.shape[0], o.shape[1], smoothing, hw, kw, temp)
+        ctx.o, ctx.t, ctx.plan, ctx.cfg = o, (y, teacher, weight), plan, cfg
+        holder.last_terms = loss
+        return loss[:1].view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        o, plan = ctx.o, ctx.plan
+        y, teacher, weight = ctx.t
+        smoothing, hw, kw, temp = ctx.cfg
+        n = o.numel()
+        dz = plan.dout if (plan is not None and plan.dout is not None and plan.dout.numel() >= n) else \
+            torch.empty(n, dtype=torch.float32, device=o.device)
+        scratch = torch.empty(3, dtype=torch.float32, device=o.device)
+        gs = g.detach().float().reshape(1).contiguous()
+        lib.mi355_ce_distill(o, y, teacher, weight, scratch, dz, gs, o.shape[0], o.shape[1], smoothing, hw, kw, temp)
+        return dz[:n].view(o.shape), None, None, None, None, None, None
+
+
+class DistillCrossEntropyLoss(MixCrossEntropyLoss):
+    """(1 - kd_weight) CE + kd_weight T^2 KL(softmax(v / T) || softmax(z / T)) (batch mean) against a ``utils.distill.DistillTarget`` —
+    hard labels and a frozen teacher's logits v — one autograd node evaluated in double (mi355_ce_distill).  CE is
+    ``MixCrossEntropyLoss(label_smoothing, weight)`` on hard labels, with its normalisation (the sum is divided by B).  With a plain
+    label tensor — the validation loop — the loss is that unscaled hard loss through ``MixCrossEntropyLoss``'s own launch, bit for
+    bit.  No mixed targets: train() rejects mixup / CutMix next to it.  ``last_terms``: the device tensor [total, hard, KD] of the
+    last distilled call, as the kernel leaves it (no synchronisation): CE and KD unweighted, total = (1 - kd_weight) CE + kd_weight KD."""
+
+    accepts_mixed_target = False
+    accepts_distill_target = True
+
+    def __init__(self, kd_weight=0.5, temperature=4.0, label_smoothing=0.0, weight=None, check_labels=False):
+        super().__init__(label_smoothing, weight, check_labels)
+        _check_kd(kd_weight, temperature)
+        self.kd_weight, self.temperature = float(kd_weight), float(temperature)
+        self.last_terms = None
+
+    def forward(self, out, target):
+        if hasattr(target, "ya"):
+            raise ValueError("DistillCrossEntropyLoss takes hard labels: distillation on a mixed target (mixup / CutMix) is not built")
+        if not hasattr(target, "teacher_logits"):
+            return super().forward(out, target)
+        plan = getattr(out, "_mi355_plan", None)
+        out = out.float()
+        if out.dim() != 2:
+            raise ValueError(f"logits [B, C] expected, got {tuple(out.shape)}")
+        B, C = out.shape
+        y = target.hard
+        if y.dim() != 1 or y.size(0) != B or y.dtype.is_floating_point:
+            raise ValueError(f"an integer label tensor [{B}] expected, got {y.dtype} {tuple(y.shape)}")
+        if (self.check_labels or not y.is_cuda) and (int(y.min()) < 0 or int(y.max()) >= C):
+            raise ValueError(f"labels must lie in [0, {C}), got {y.tolist()}")
+        v = _teacher_like(out, target)
+        dev = out.device
+        y = y.to(dev, torch.int64).contiguous()
+        w = self.weight
+        if w is not None:
+            if w.numel() != C:
+                raise ValueError(f"weight holds {w.numel()} classes, the logits {C}")
+            if w.device != dev:
+                self.weight = w = w.to(dev)
+        cfg = (self.label_smoothing, 1.0 - self.kd_weight, self.kd_weight, self.temperature)
+        return _CEDistillFn.apply(out, y, v, w, cfg, plan, self)
+
+    def extra_repr(self):
+        return f"kd_weight={self.kd_weight}, temperature={self.temperature}, " + super().extra_repr()
+
+
 # ---- multi-class segmentation (csrc/mcseg.hip) ---------------------------------------------------------------------------------
 MCSEG_ROW = 50      # MI355_MCSEG_ROW of include/mi355conv.h: doubles per partial row
 

@@ -18,6 +18,10 @@ the parameter list stays as it is here too), ``averaging`` a dict such as ``{"mo
 ``{"mode": "swa", "swa_start": E}``, or a ``mi355.averaging.WeightAverage``: an average of the weights along the trajectory, validated
 and saved beside the raw model (``{name}_ema_best_loss.pt`` / ``{name}_ema_best_acc.pt``, ``{name}_swa.pt``); the raw model's lines,
 schedule and files do not change.
+A ``utils.distill.Distilled(train_dl, teacher)`` in the place of ``train_dl`` (inside a ``WithAveraging``, outside a ``MixedBatches``):
+knowledge distillation — the frozen teacher's eval forward on every training batch, the target a ``DistillTarget`` for
+``mi355.nn.SegDistillationLoss`` / ``DistillCrossEntropyLoss``, one more line per epoch (``Distill hard … | KD …``); validation stays
+on the hard target alone.
 
 Data parallel: when ``torch.distributed`` is initialised with more than one rank (``torchrun --nproc-per-node N
 utils/trainer.py ...``), ``train()`` shards the loaders' batches by rank (utils/distributed.py), wraps the model in
@@ -149,6 +153,20 @@ def _averaging_spec(averaging, epochs):
 
 
 def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False, cls_head_name=None, criterion=None):
+    # a utils.distill.Distilled among the wrappers of train_dl: its teacher runs in eval mode and gets its previous mode back, however
+    # the run ends
+    teacher, dl = None, train_dl
+    while dl is not None and teacher is None:
+        teacher, dl = getattr(dl, "teacher", None), getattr(dl, "loader", None)
+    was_training = bool(getattr(teacher, "training", False))
+    try:
+        return _train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg, cls_head_name, criterion)
+    finally:
+        if was_training:
+            teacher.train()
+
+
+def _train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg, cls_head_name, criterion):
     device = torch.device(device)
     # train_dl may be a mi355.averaging.WithAveraging(loader, averaging): the loader is used as it would be without the wrapper and
     # an average of the weights is kept beside the raw model (below); a plain loader = today's loop
@@ -157,6 +175,16 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         train_dl, averaging = train_dl.loader, train_dl.averaging
         if averaging is not None:
             averaging, avg_mode, swa_start = _averaging_spec(averaging, epochs)
+    # train_dl may be a utils.distill.Distilled(loader, teacher): the loader is used as it would be without the wrapper and every
+    # TRAINING batch's target becomes a DistillTarget(y, teacher's logits on x); a plain loader = today's loop
+    teacher = None
+    if hasattr(train_dl, "teacher"):
+        train_dl, teacher = train_dl.loader, train_dl.teacher
+    _ORDER = "WithAveraging(Distilled(MixedBatches(loader, batch_mix), teacher), averaging)"
+    if teacher is not None and hasattr(train_dl, "averaging"):
+        raise TypeError(f"WithAveraging goes OUTSIDE Distilled: train(model, {_ORDER}, ...)")
+    if hasattr(train_dl, "batch_mix") and hasattr(train_dl.loader, "teacher"):
+        raise TypeError(f"Distilled goes OUTSIDE MixedBatches (the teacher sees the mixed batch): train(model, {_ORDER}, ...)")
     model = model.to(device)
     if hasattr(model, "engine"):
         model.engine._check_storage()                 # flat fp32 parameter / gradient buffers
@@ -169,6 +197,15 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         train_dl, batch_mix = train_dl.loader, train_dl.batch_mix
     if hasattr(train_dl, "averaging"):
         raise TypeError("WithAveraging goes OUTSIDE MixedBatches: train(model, WithAveraging(MixedBatches(loader, batch_mix), averaging), ...)")
+    if teacher is not None:
+        if batch_mix is not None and not seg:
+            raise ValueError("Distilled next to a classifier batch_mix: distillation on a MixedTarget (mixup / CutMix labels) is not built; "
+                             "use one of the two")
+        if criterion is None:
+            criterion = mnn.SegDistillationLoss(1.0, 0.0) if seg else mnn.DistillCrossEntropyLoss(label_smoothing=0.1)
+        elif not getattr(criterion, "accepts_distill_target", False):
+            raise TypeError(f"Distilled turns the target into a DistillTarget, which {type(criterion).__name__} cannot take: use "
+                            f"mi355.nn.{'SegDistillationLoss' if seg else 'DistillCrossEntropyLoss'}")
     if batch_mix is not None:
         if bool(getattr(batch_mix, "seg", seg)) != bool(seg):
             raise ValueError(f"batch_mix was built with seg={batch_mix.seg} but train() runs with seg={seg}")
@@ -232,6 +269,13 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         avg = averaging if isinstance(averaging, WeightAverage) else WeightAverage(model, **averaging)
         avg_best = float("inf") if seg else 0.0
 
+    # distillation (None = off): the frozen teacher runs forward only, in eval mode for the whole run (its previous mode is put back
+    # at the end); data parallel: every rank runs its own replica, nothing of it is communicated
+    if teacher is not None:
+        from utils.distill import DistillTarget, teacher_logits
+        if getattr(teacher, "training", False):
+            teacher.eval()
+
     def validate():
         """one pass over val_dl in eval mode -> (loss sum, metric sum) on the device"""
         model.eval()
@@ -290,10 +334,13 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         hit_sum = torch.zeros((), device=device)
         seen = 0
         seen_all = 0                                  # samples this rank trained on (padding batches of the last step included)
+        kd_sums = torch.zeros(2, device=device) if teacher is not None else None      # hard and KD term, sample-weighted
         for x, y in train_dl:
             x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
             if batch_mix is not None:
                 x, y = batch_mix(x, y)
+            if teacher is not None:
+                y = DistillTarget(y, teacher_logits(teacher, x))      # (segmentation CutMix: the teacher sees the mixed image)
             optimizer.zero_grad(set_to_none=True)
             out = model(x)
             if seg and out.dim() == 3:
@@ -308,8 +355,10 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
             scaler.update()
             loss_sum += loss.detach() * x.size(0)
             seen_all += x.size(0)
+            if teacher is not None:
+                kd_sums += criterion.last_terms[1:3] * x.size(0)
             if not seg:
-                hit_sum += (torch.argmax(out.detach(), 1) == (y if batch_mix is None else getattr(y, "hard", y))).sum()
+                hit_sum += (torch.argmax(out.detach(), 1) == (y if batch_mix is None and teacher is None else getattr(y, "hard", y))).sum()
                 seen += y.size(0)
 
         if dp is not None:
@@ -320,7 +369,12 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
         # optimiser step makes the number of samples trained on larger than the dataset, so the mean divides by what was seen)
         if dp is not None:
             cnt = torch.tensor([float(seen_all), float(seen)], device=device, dtype=torch.float64)
-            loss_sum, hit_sum, vloss, vmetric, seen_all_t, seen_t = all_reduce_sums(loss_sum, hit_sum, vloss, vmetric, cnt[0], cnt[1])
+            if teacher is None:
+                loss_sum, hit_sum, vloss, vmetric, seen_all_t, seen_t = all_reduce_sums(loss_sum, hit_sum, vloss, vmetric, cnt[0], cnt[1])
+            else:
+                loss_sum, hit_sum, vloss, vmetric, seen_all_t, seen_t, kd_h, kd_k = all_reduce_sums(
+                    loss_sum, hit_sum, vloss, vmetric, cnt[0], cnt[1], kd_sums[0], kd_sums[1])
+                kd_sums = torch.stack([kd_h, kd_k])
             n_train_seen, seen = int(seen_all_t.item()), int(seen_t.item())
         else:
             n_train_seen = n_train
@@ -337,6 +391,9 @@ def train(model, train_dl, val_dl, device, epochs, lr, name, save_dir, seg=False
             score = val_acc
             say(f"[{name}] Ep{epoch}: TrainLoss {train_loss:.3f} (Acc {train_acc:.2f}%) | ValLoss {val_loss:.3f} | ValAcc {val_acc:.2f}%")
             improved = val_acc > best_score
+        if teacher is not None:
+            kd_h, kd_k = (kd_sums / n_train_seen).tolist()      # the epoch's means of the two terms as the kernels report them (criterion.last_terms)
+            say(f"[{name}] Ep{epoch}: Distill hard {kd_h:.3f} | KD {kd_k:.3f}")
 
         if seg or epoch <= STAGE1:
             scheduler.step()

@@ -18,6 +18,7 @@ defaults to synthetic 256x256 batches so that it runs anywhere:
     python utils/trainer.py --task seg --model attentionunet --seg-loss focal_tversky --tversky-alpha 0.3 --tversky-beta 0.7
     python utils/trainer.py --task seg --model attentionunet --seg-loss focal_dice --focal-gamma 2 --focal-alpha 0.25
     python utils/trainer.py --task cls --model resnet18 --cls-loss focal --focal-gamma 2 --class-weight balanced
+    python utils/trainer.py --task seg --model resnetunet --teacher weights/segmentation_models/attentionunet_best_loss.pt --teacher-model attentionunet
 
 With ``--data-root dataset`` (the reference's DATA_ROOT layout: ``splits/train.csv``, ``<class>/images|masks/<id>.png``) it reads the
 real files instead: two dataset objects per task with the train / val transforms, one 80/20 index split shared by both
@@ -160,7 +161,68 @@ def build_parser():
                     help="stochastic weight averaging: the equal-weight average of the weights at the end of every epoch from this one "
                          "(1-based) on, BatchNorm statistics re-estimated on the training data, saved as {name}_swa.pt "
                          "(tester.py --weights-variant swa); off by default; not together with --ema-decay")
+    ap.add_argument("--teacher", default=None,
+                    help="knowledge distillation (Hinton et al. 2015; utils/distill.py): checkpoint of a trained model of --teacher-model "
+                         "whose logits every training batch is also matched against; needs one --task; off by default")
+    ap.add_argument("--teacher-model", default=None, help="--teacher: the teacher's model name (any name --model takes for the task)")
+    ap.add_argument("--kd-weight", type=float, default=0.5,
+                    help="--teacher: loss = (1 - w) * hard loss + w * T^2 * KL(teacher || student); in [0, 1]")
+    ap.add_argument("--kd-temperature", type=float, default=None, help="--teacher: the temperature T; default 2 (seg) / 4 (cls)")
     return ap
+
+
+def distill_arg(args):
+    """--teacher / --teacher-model: None without them (today's loop), else dict(path, model, kd_weight, temperature), after a clear
+    error for a half-given pair, for what the distillation losses are not combined with and for values out of range — raised here,
+    before any data is read."""
+    if args.teacher is None and args.teacher_model is None:
+        return None
+    if args.teacher is None or args.teacher_model is None:
+        raise ValueError("--teacher (a checkpoint) and --teacher-model (its model name) go together")
+    if args.task == "both":
+        raise ValueError("--teacher with --task both: one teacher fits one task; run --task seg and --task cls separately")
+    if args.task == "seg":
+        if args.seg_loss not in ("bce", "dice", "bce_dice"):
+            raise ValueError(f"--teacher: the distillation loss adds its term to --seg-loss bce|dice|bce_dice (got {args.seg_loss})")
+        bad = [flag for flag, on in (("--boundary-weight", args.boundary_weight != 0), ("--lovasz-weight", args.lovasz_weight != 0),
+                                     ("--seg-classes > 1", int(args.seg_classes) != 1)) if on]
+        if bad:
+            raise ValueError(f"--teacher: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} not combined with distillation "
+                             "(binary BCE / Dice + KD is what is built)")
+    else:
+        bad = [flag for flag, on in (("--cls-loss focal", args.cls_loss == "focal"), ("--mixup-alpha", args.mixup_alpha != 0),
+                                     ("--cutmix-alpha", args.cutmix_alpha != 0)) if on]
+        if bad:
+            raise ValueError(f"--teacher with --task cls: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} not combined with "
+                             "distillation (hard labels under cross-entropy + KD is what is built)")
+    fin = float("inf")
+    if not 0 <= args.kd_weight <= 1:
+        raise ValueError(f"--kd-weight must lie in [0, 1] ({args.kd_weight})")
+    temp = (2.0 if args.task == "seg" else 4.0) if args.kd_temperature is None else args.kd_temperature
+    if not 0 < temp < fin:
+        raise ValueError(f"--kd-temperature must be a finite number > 0 ({temp})")
+    if args.task == "seg" and not (0 <= args.bce_weight < fin and 0 <= args.dice_weight < fin):
+        raise ValueError(f"--bce-weight and --dice-weight must be finite and not negative ({args.bce_weight}, {args.dice_weight})")
+    return dict(path=args.teacher, model=args.teacher_model, kd_weight=float(args.kd_weight), temperature=float(temp))
+
+
+def distill_criterion(args, kd, weight=None):
+    """The loss of a distilled run (distill_arg has checked the flags): mi355.nn.SegDistillationLoss with --seg-loss's hard terms, or
+    mi355.nn.DistillCrossEntropyLoss(label smoothing 0.1, ``weight`` from --class-weight balanced)."""
+    from mi355 import nn as mnn
+    if args.task == "seg":
+        bw, dw = {"bce": (1.0, 0.0), "dice": (0.0, 1.0), "bce_dice": (args.bce_weight, args.dice_weight)}[args.seg_loss]
+        return mnn.SegDistillationLoss(bw, dw, per_sample=args.dice_per_sample, kd_weight=kd["kd_weight"], temperature=kd["temperature"])
+    return mnn.DistillCrossEntropyLoss(kd["kd_weight"], kd["temperature"], label_smoothing=0.1, weight=weight)
+
+
+def load_teacher(kd, task, device):
+    """The frozen teacher of a distilled run: --teacher-model with the weights of --teacher on ``device``, in eval mode, no gradients."""
+    model = get_seg_model(kd["model"]) if task == "seg" else get_class_model(kd["model"])[0]
+    model.load_state_dict(torch.load(kd["path"], map_location="cpu"))
+    for p in model.parameters():
+        p.requires_grad = False
+    return model.to(device).eval()
 
 
 def averaging_arg(args):
@@ -437,6 +499,7 @@ def main():
         focal_arg(args)
     cls_loss_arg(args)
     averaging = averaging_arg(args)
+    kd = distill_arg(args)
     variant = None if averaging is None else averaging["mode"]
     seg_labels = {"labels": True} if multi else {}
     for task in tasks:
@@ -465,12 +528,18 @@ def main():
         if mixes[task] is not None:
             from utils.mix import MixedBatches
             train_dl = MixedBatches(train_dl, mixes[task])
+        if kd is not None:
+            from utils.distill import Distilled
+            train_dl = Distilled(train_dl, load_teacher(kd, task, device))
+            say(f"distillation: teacher {kd['model']} from {kd['path']}, kd weight {kd['kd_weight']}, temperature {kd['temperature']}")
         if averaging is not None:
             from mi355.averaging import WithAveraging
             train_dl = WithAveraging(train_dl, dict(averaging))
         cls_crit = None
         if task == "cls":
             cls_crit = cls_criterion(args, mixes[task], ds_tr if args.data_root else None, perm[:n_train] if args.data_root else None, say)
+            if kd is not None:
+                cls_crit = distill_criterion(args, kd, None if cls_crit is None else cls_crit.weight)
         for name in names:
             say(f"\n{'=' * 20} {task.upper()} :: {name} {'=' * 20}")
             if task == "cls":
@@ -484,7 +553,7 @@ def main():
             else:
                 model = get_seg_model(name, classes=args.seg_classes)
                 best = train(model, train_dl, val_dl, device, args.epochs, args.lr, name, os.path.join(args.save_dir, "segmentation_models"), seg=True,
-                             criterion=seg_criterion(args))
+                             criterion=seg_criterion(args) if kd is None else distill_criterion(args, kd))
                 if args.calibrate:
                     calibrate_checkpoint(model, val_dl, device, name, os.path.join(args.save_dir, "segmentation_models"), True, say)
                     if variant is not None:
